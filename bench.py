@@ -9,13 +9,22 @@ speedup vs fp32". Synthetic data of the real pre-training shapes, random-init we
 The model is wrapped in apex DDP at every N (at N=1 over a one-rank RCCL group), so the
 gradient hooks, bucket views and bucket all-reduces are inside the timed region at 1 GPU too.
 
-After the timed bf16 loop a second, shorter pass runs the SAME step in fp32 (amp O0, same
-per-GPU batch: micro-batches of ``--fp32-microbatch`` accumulated, because fp32 activations
-of 768 sequences do not fit) and reports ``speedup_vs_fp32`` = fp32 ms/step / bf16 ms/step —
-the second half of the metric. ``--no-fp32`` skips it.
+A plain run (``--gpus N --steps K --warmup W``) sets up, warms up, times the K bf16 steps and
+prints the result line; nothing else runs. ``--dump-outputs DIR`` also writes what the last timed
+step computed (its loss and a fixed, seeded sample of the updated weights) as ``DIR/<name>.npy``,
+so two builds can be compared output for output: the same arguments give the same inputs.
+
+``--full`` adds every other measurement. After the timed bf16 loop a second, shorter pass runs
+the SAME step in fp32 (amp O0, same per-GPU batch: micro-batches of ``--fp32-microbatch``
+accumulated, because fp32 activations of 768 sequences do not fit) and reports
+``speedup_vs_fp32`` = fp32 ms/step / bf16 ms/step — the second half of the metric
+(``--no-fp32`` skips it); on one GPU the fp8 pass runs too (``--no-fp8`` skips it; ``--fp8`` asks
+for it at N > 1), ``--fp16`` adds the fp16 dynamic-loss-scale pass, and at N > 1 the bucket-sized
+all-reduce probe runs.
 
 Usage:
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--seq S] [--fp32-only]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--seq S] [--dump-outputs DIR]
+                  [--full [--no-fp32] [--no-fp8] [--fp8] [--fp16]] [--fp32-only]
   (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 Rank 0 prints ONE JSON line on stdout.
 """
@@ -44,19 +53,26 @@ def parse():
     ap.add_argument("--batch", type=int, default=int(os.environ.get("APEX_BENCH_BATCH", 768)),
                     help="per-GPU sequences per step")
     ap.add_argument("--seq", type=int, default=128)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also run the other measurements: the fp32 pass "
+                         "(speedup_vs_fp32), on one GPU the fp8 pass, the passes asked for with --fp8 / --fp16, "
+                         "and at N > 1 the all-reduce probe; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (loss.npy, and weights.npy / "
+                         "master_weights.npy: a fixed, seeded sample of the updated weights) as float32 under DIR")
     ap.add_argument("--fp32-only", action="store_true", help="time only the fp32 (amp O0) step")
-    ap.add_argument("--no-fp32", action="store_true", help="skip the fp32 speedup pass")
+    ap.add_argument("--no-fp32", action="store_true", help="with --full: skip the fp32 speedup pass")
     ap.add_argument("--fp32-steps", type=int, default=2)
     ap.add_argument("--fp32-microbatch", type=int, default=256)
     ap.add_argument("--layers", type=int, default=24, help="(debug only; the metric needs 24)")
     ap.add_argument("--fp8", action="store_true",
-                    help="extra pass: the same step with amp fp8=True (NOT the headline: reported under extra.fp8); "
-                         "on by default for a 1-GPU run")
-    ap.add_argument("--no-fp8", action="store_true", help="skip the default 1-GPU fp8 pass")
+                    help="with --full, extra pass: the same step with amp fp8=True (NOT the headline: reported under "
+                         "extra.fp8); on by default for a 1-GPU --full run")
+    ap.add_argument("--no-fp8", action="store_true", help="with --full: skip the default 1-GPU fp8 pass")
     ap.add_argument("--fp8-steps", type=int, default=10)
     ap.add_argument("--fp16", action="store_true",
-                    help="extra pass: the same step as amp O2 fp16 with DYNAMIC loss scaling (the reference's O2; "
-                         "times the device-side overflow check / skip path; reported under extra.fp16)")
+                    help="with --full, extra pass: the same step as amp O2 fp16 with DYNAMIC loss scaling (the "
+                         "reference's O2; times the device-side overflow check / skip path; reported under extra.fp16)")
     ap.add_argument("--fp16-steps", type=int, default=10)
     # DDP bucket sizes (elements): at N>1 chosen by an in-job probe of the communicator unless
     # given here (apex.parallel.preflight.select_bucket_sizes); at N=1 there is no communication
@@ -70,6 +86,8 @@ def parse():
                          "DDP -> timed steps -> max over ranks -> one JSON line) on CPU over gloo with a tiny "
                          "BERT, so the multi-GPU path is exercised where no GPUs are (tests/test_bench_rehearsal.py)")
     args = ap.parse_args()
+    if (args.fp8 or args.fp16) and not args.full:
+        ap.error("--fp8 / --fp16 ask for an extra pass: give --full with them")
     if args.cpu_rehearsal:
         os.environ.setdefault("APEX_DIST_BACKEND", "gloo")
         if "--batch" not in " ".join(sys.argv):
@@ -130,6 +148,51 @@ def make_step(model, opt, batches, micro):
 def _sync(env):
     if env.device.type == "cuda":
         torch.cuda.synchronize()
+
+
+def extra_passes(args, world, rehearsal):
+    """Which measurements run besides the headline loop. All of them belong to ``--full``: the fp8
+    pass (default on one GPU so the round-end record carries its speedup, opt-in with ``--fp8`` at
+    N > 1, never in a rehearsal unless asked for), the ``--fp16`` pass, the all-reduce probe at
+    N > 1 and the fp32 pass; ``--fp32-only`` times the fp32 step alone, with or without ``--full``."""
+    extras = args.full and not args.fp32_only
+    return {
+        "fp8": bool(extras and (args.fp8 or (world == 1 and not args.no_fp8 and not rehearsal))),
+        "fp16": bool(extras and args.fp16),
+        "allreduce_probe": bool(extras and world > 1),
+        "fp32": bool(args.fp32_only or (args.full and not args.no_fp32)),
+    }
+
+
+def dump_outputs(env, directory, loss, model, opt, per_tensor=4096):
+    """Write what the last timed step returned to its caller as ``directory/<name>.npy`` (float32):
+    the loss, and the weights the step updated — the model's (bf16 under O2) and the optimizer's
+    (the fp32 masters). Every tensor contributes at most ``per_tensor`` elements at positions drawn
+    once from a fixed seed, in parameter order, so the files hold the same positions on every run
+    (BERT-Large: 743 426 values, 3 MB per file). Rank 0 writes; DDP keeps the ranks' weights equal."""
+    import numpy as np
+
+    from apex.amp._amp_state import master_params
+
+    if not env.is_main:
+        return
+    os.makedirs(directory, exist_ok=True)
+    g = torch.Generator(device="cpu")
+    g.manual_seed(20240607)
+
+    def sample(params):
+        parts = []
+        for p in params:
+            flat = p.detach().reshape(-1)
+            if flat.numel() > per_tensor:
+                idx = torch.randint(flat.numel(), (per_tensor,), generator=g)
+                flat = flat[idx.to(flat.device)]
+            parts.append(flat.float().cpu())
+        return torch.cat(parts).numpy()
+
+    np.save(os.path.join(directory, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(directory, "weights.npy"), sample(model.parameters()))
+    np.save(os.path.join(directory, "master_weights.npy"), sample(master_params(opt)))
 
 
 def allreduce_probe(env, numel, iters=5):
@@ -229,13 +292,15 @@ def main():
         extra["ddp"] = model.comm_stats()
         if not rehearsal:
             extra["peak_mem_gb"] = round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 1)
+        if args.dump_outputs:
+            dump_outputs(env, args.dump_outputs, loss, model, opt)
         del model, opt, batches, loss
         gc.collect()
         if not rehearsal:
             torch.cuda.empty_cache()
-    # the fp8 pass runs by default on one GPU (so the round-end record carries its speedup, not only
-    # builder runs); multi-GPU runs keep it opt-in
-    if (args.fp8 or (world == 1 and not args.no_fp8 and not rehearsal)) and not args.fp32_only:
+    # everything below the headline loop belongs to --full (extra_passes)
+    run = extra_passes(args, world, rehearsal)
+    if run["fp8"]:
         # per-tensor scaled fp8 forward / input-gradient GEMMs (apex.fp8): an extension beyond the
         # metric's amp O2 bf16 configuration, so it never replaces the headline value
         from apex import fp8 as _fp8
@@ -272,8 +337,8 @@ def main():
         _fp8.disable()
         gc.collect()
         torch.cuda.empty_cache()
-    if args.fp16 and not args.fp32_only:
-        # amp O2 fp16 with dynamic loss scaling (reference semantics: /root/reference/apex/amp/scaler.py:20-55);
+    if run["fp16"]:
+        # amp O2 fp16 with dynamic loss scaling (the reference's apex/amp/scaler.py semantics);
         # the overflow check + skip decision stay on the device (no host sync in the timed steps)
         from apex.amp._amp_state import _amp_state
 
@@ -290,16 +355,18 @@ def main():
         del model, opt, batches, h_loss
         gc.collect()
         torch.cuda.empty_cache()
-    if world > 1 and not args.fp32_only:
+    if run["allreduce_probe"]:
         extra["allreduce_probe"] = allreduce_probe(env, args.message_size)
     fp32_ms = None
-    if args.fp32_only or not args.no_fp32:
+    if run["fp32"]:
         model, opt = build(env, cfg, True, args.message_size)
         batches = batches_for(args.batch)
-        f_el, _ = time_steps(env, make_step(model, opt, batches, args.fp32_microbatch),
-                             max(1, args.fp32_steps), 1)
+        f_el, f_loss = time_steps(env, make_step(model, opt, batches, args.fp32_microbatch),
+                                  max(1, args.fp32_steps), 1)
         fp32_ms = f_el / max(1, args.fp32_steps) * 1000.0
-        del model, opt, batches
+        if args.fp32_only and args.dump_outputs:
+            dump_outputs(env, args.dump_outputs, f_loss, model, opt)
+        del model, opt, batches, f_loss
         gc.collect()
         if not rehearsal:
             torch.cuda.empty_cache()

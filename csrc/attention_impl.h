@@ -1093,8 +1093,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D <= 6
   lds_barrier();  // every wave is done reading lds_k (dQ products)
   constexpr int LDE = kBwdBK + 4;
   static_assert(D * LDE <= LDSK, "dK/dV staging fits lds_k");
+  // DSUM: the four waves' column sums (32 keys each) meet in LDS and are added in wave order, so
+  // the bias gradient does not depend on which wave's atomic lands first (four float atomics on one
+  // slot rounded differently from run to run). lds_q is free here: its last reads (the final query
+  // block's products) are behind the barrier above. One [waves][D] image per emit call.
+  static_assert(2 * kBwdWaves * D * sizeof(float) <= kBwdBQ * LDQ * sizeof(T), "column-sum staging fits lds_q");
   auto emit = [&](const f32x16 (&acc)[D / 32], const float mul, T* dst, const int64_t ss, float* dsum_t,
-                  uint8_t* q8dst) {
+                  uint8_t* q8dst, float* fsum) {
     typedef T t4 __attribute__((ext_vector_type(4)));
 #pragma unroll
     for (int db = 0; db < D / 32; ++db) {
@@ -1112,10 +1117,18 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D <= 6
       }
       if constexpr (DSUM) {
         sum += xor32_f(sum);
-        if (hl == 0) atomicAdd(dsum_t + 32 * db + r, sum);
+        if (hl == 0) fsum[wid * D + 32 * db + r] = sum;
       }
     }
     lds_barrier();
+    if constexpr (DSUM) {
+      // one contribution per workgroup and slot (several key blocks of one head still meet here)
+      if (threadIdx.x < D) {
+        const float* f = fsum + threadIdx.x;
+        static_assert(kBwdWaves == 4, "fixed-order sum over the four waves");
+        atomicAdd(dsum_t + threadIdx.x, ((f[0] + f[D]) + f[2 * D]) + f[3 * D]);
+      }
+    }
     // 16-lane group tasks: (8-dim block, 16-key block); a wave's 4 groups take 4 consecutive dim
     // blocks of the same keys (64 contiguous bytes of each key row per store instruction)
     constexpr int NDB = D / 8, NTASK = NDB * (kBwdBK / 16);
@@ -1169,9 +1182,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D <= 6
     lds_barrier();
   };
   emit(dk, a.scale, dkp, a.dk_ss, DSUM ? dsum + (int64_t)a.H * D : nullptr,
-       a.q8dk ? a.q8dk + b * a.dk_bs + h * a.dk_hs : nullptr);
+       a.q8dk ? a.q8dk + b * a.dk_bs + h * a.dk_hs : nullptr, (float*)lds_q);
   emit(dv, rkeep, dvp, a.dv_ss, DSUM ? dsum + (int64_t)2 * a.H * D : nullptr,
-       a.q8dv ? a.q8dv + b * a.dv_bs + h * a.dv_hs : nullptr);
+       a.q8dv ? a.q8dv + b * a.dv_bs + h * a.dv_hs : nullptr, (float*)lds_q + kBwdWaves * D);
   if (a.q8dq) f8_block_amax(q8mx, a.q8_amax, q8seen);  // every thread of the block reaches this
 }
 

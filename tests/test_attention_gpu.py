@@ -130,3 +130,30 @@ def test_attention_bwd_bias_colsums(S, causal):
     torch.testing.assert_close(dsum, ref, rtol=2e-3, atol=2e-2)
     db = C.partial_colsum(dsum, torch.float32)
     torch.testing.assert_close(db, ref.sum(0), rtol=2e-3, atol=5e-2)
+
+
+def test_attention_bwd_bias_colsums_repeat_bitwise():
+    """The single-kernel backward (Sk <= 128) adds its four waves' column sums in a fixed order: the
+    same inputs give the same bits on every launch (BERT's shape; with four float atomics per slot
+    about one slot in a few hundred thousand changed its last bit from launch to launch)."""
+    import apex._ext as e
+
+    C = e.require()
+    torch.manual_seed(5)
+    B, S, H, D = 256, 128, 16, 64
+    qkv = torch.randn(B, S, 3, H, D, device="cuda").bfloat16()
+    q, k, v = qkv.unbind(2)
+    scale = D ** -0.5
+    o, lse, dmask = C.flash_attn_fwd(q, k, v, False, scale, 0.0, 0, 0, None)
+    do = torch.randn_like(o)
+    dqkv = torch.empty_like(qkv)
+    dq, dk, dv = dqkv.unbind(2)
+    first = None
+    for _ in range(10):
+        dsum = torch.zeros(B, 3 * H * D, device="cuda")
+        C.flash_attn_bwd(do, q, k, v, o, lse, dq, dk, dv, False, scale, 0.0, 0, 0, None, dmask, dsum)
+        if first is None:
+            first = dsum
+            torch.testing.assert_close(dsum, dqkv.float().sum(1).reshape(B, 3 * H * D), rtol=2e-3, atol=2e-2)
+        else:
+            assert torch.equal(dsum, first)

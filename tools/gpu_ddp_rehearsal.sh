@@ -7,7 +7,7 @@ O=gpurun_out/${OUT:-ddp}
 mkdir -p $O
 export PYTHONUNBUFFERED=1 APEX_DIST_BACKEND=gloo APEX_DIST_SHARE_GPU=1
 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 \
-  bench.py --gpus 2 --steps 4 --warmup 2 --layers 2 --batch 32 > $O/bert2.json 2> $O/bert2.err || { tail -30 $O/bert2.err; exit 4; }
+  bench.py --gpus 2 --full --steps 4 --warmup 2 --layers 2 --batch 32 > $O/bert2.json 2> $O/bert2.err || { tail -30 $O/bert2.err; exit 4; }
 cat $O/bert2.json
 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 \
   benchmarks/resnet50.py --steps 3 --warmup 1 --batch 16 > $O/rn2.json 2> $O/rn2.err || { tail -30 $O/rn2.err; exit 5; }

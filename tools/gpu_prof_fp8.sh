@@ -5,6 +5,6 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/${OUT:-proff8}
 mkdir -p $O
-timeout -k 10 600 rocprofv3 --kernel-trace -d $O/bert -o prof --output-format csv -- python bench.py --steps 5 --warmup 2 --fp8 > $O/bert.json 2> $O/bert.err || exit 3
+timeout -k 10 600 rocprofv3 --kernel-trace -d $O/bert -o prof --output-format csv -- python bench.py --full --steps 5 --warmup 2 --fp8 > $O/bert.json 2> $O/bert.err || exit 3
 tail -c 300 $O/bert.json
 echo "all done"

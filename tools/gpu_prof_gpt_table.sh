@@ -12,7 +12,7 @@ for t in none tab; do
 done
 unset APEX_WGRAD_TT_TABLE
 for r in 1 2 3; do
-  APEX_WGRAD_TT_TABLE="1024x1024:65536:16" timeout -k 10 400 python bench.py > $O/bert_tab_$r.json 2>/dev/null || exit 4
-  APEX_WGRAD_TT_TABLE=none timeout -k 10 400 python bench.py > $O/bert_none_$r.json 2>/dev/null || exit 4
+  APEX_WGRAD_TT_TABLE="1024x1024:65536:16" timeout -k 10 400 python bench.py --full > $O/bert_tab_$r.json 2>/dev/null || exit 4
+  APEX_WGRAD_TT_TABLE=none timeout -k 10 400 python bench.py --full > $O/bert_none_$r.json 2>/dev/null || exit 4
 done
 echo "all done"

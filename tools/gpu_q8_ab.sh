@@ -11,5 +11,5 @@ timeout -k 10 400 python -u -m pytest tests/test_fp8_gpu.py tests/test_attention
   || { tail -30 $O/pytest.log; exit 3; }
 tail -2 $O/pytest.log
 bash tools/gpu_so_ab.sh ${OUT:-q8ab}/prod 2 "python tools/f8_producer_bench.py"
-bash tools/gpu_so_ab.sh ${OUT:-q8ab}/bench 1 "python bench.py --steps 10 --warmup 3 --fp8"
+bash tools/gpu_so_ab.sh ${OUT:-q8ab}/bench 1 "python bench.py --full --steps 10 --warmup 3 --fp8"
 echo done

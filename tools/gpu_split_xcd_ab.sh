@@ -13,6 +13,6 @@ for r in 1 2; do
 done
 for r in 1 2; do
   for x in 0 1; do
-    APEX_GEMM_SPLIT_XCD=$x timeout -k 10 400 python bench.py > "$OUT/bench_x${x}_$r.json" 2> "$OUT/bench_x${x}_$r.err"
+    APEX_GEMM_SPLIT_XCD=$x timeout -k 10 400 python bench.py --full > "$OUT/bench_x${x}_$r.json" 2> "$OUT/bench_x${x}_$r.err"
   done
 done

@@ -9,8 +9,8 @@ mkdir -p "$OUT"
 BERT=${BERT_TABLE:-"1024x1024:65536:16"}
 GPT=${GPT_TABLE:-"1600x1600:16384:4,6400x1600:16384:4,1600x6400:16384:4"}
 for r in 1 2; do
-  APEX_WGRAD_TT_TABLE=none timeout -k 10 400 python bench.py > "$OUT/bert_none_$r.json" 2> "$OUT/bert_none_$r.err"
-  APEX_WGRAD_TT_TABLE="$BERT" timeout -k 10 400 python bench.py > "$OUT/bert_tab_$r.json" 2> "$OUT/bert_tab_$r.err"
+  APEX_WGRAD_TT_TABLE=none timeout -k 10 400 python bench.py --full > "$OUT/bert_none_$r.json" 2> "$OUT/bert_none_$r.err"
+  APEX_WGRAD_TT_TABLE="$BERT" timeout -k 10 400 python bench.py --full > "$OUT/bert_tab_$r.json" 2> "$OUT/bert_tab_$r.err"
 done
 for r in 1 2; do
   APEX_WGRAD_TT_TABLE=none timeout -k 10 400 python benchmarks/gpt2.py > "$OUT/gpt_none_$r.json" 2> "$OUT/gpt_none_$r.err"

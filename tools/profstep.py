@@ -6,7 +6,7 @@ generation, first-iteration bucket layout) into its totals. This reads the per-d
 using the optimizer's final kernel (LAMB stage 2 by default) as the step boundary.
 
   python tools/profstep.py <kernel_trace.csv> [k=3] [top=30] [boundary=lamb_stage2] [skip=0]
-(skip: leave out the last `skip` steps, e.g. to read the bf16 pass of a `bench.py --fp8` trace)
+(skip: leave out the last `skip` steps, e.g. to read the bf16 pass of a `bench.py --full --fp8` trace)
 Prints ms/step per kernel name (summed over dispatches), the step wall span and the GPU-busy
 fraction (sum of kernel time / span).
 """
