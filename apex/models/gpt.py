@@ -21,6 +21,7 @@ from torch import nn
 from ..normalization import FusedLayerNorm
 from ..ops import blocks as fblocks
 from ..ops import fused as fops
+from ..transformer.functional import fused_rope
 
 
 # APEX_GPT_FUSED_LN=0: per-block forward (separate LayerNorms; A/B and fallback switch)
@@ -37,6 +38,14 @@ class GPTConfig:
     layer_norm_eps: float = 1e-5
     initializer_range: float = 0.02
     pad_vocab_to: int = 64
+    position_embedding_type: str = "learned"  # "learned" | "rope"
+    rotary_percent: float = 1.0
+    rotary_base: int = 10000
+
+    def __post_init__(self):
+        if self.position_embedding_type not in ("learned", "rope"):
+            raise ValueError(f"position_embedding_type must be 'learned' or 'rope', got "
+                             f"{self.position_embedding_type!r}")
 
     @property
     def padded_vocab(self):
@@ -68,10 +77,17 @@ class GPTBlock(nn.Module):
         self.mlp_proj = nn.Linear(4 * c.n_embd, c.n_embd)
         self.p = c.dropout
 
-    def forward(self, x):
+    def _rotate(self, qkv, rope):
+        # rope = (cos, sin) [S, d2] fp32 or None (learned positions). No fp8 interaction: the fp8
+        # codes-only paths live in apex.ops.blocks' whole-sublayer Functions, which this attention
+        # sublayer does not use (QKV GEMM, this rotation and the flash kernel are separate ops).
+        return qkv if rope is None else fused_rope.apply_rotary_qkv_packed(qkv, rope[0], rope[1])
+
+    def forward(self, x, rope=None):
         B, S, E = x.shape
         p = self.p if self.training else 0.0
         qkv = fops.fused_dense(self.ln_1(x), self.c_attn.weight, self.c_attn.bias).view(B, S, 3, self.h, self.d)
+        qkv = self._rotate(qkv, rope)
         ctx = fops.attention_qkv_packed(qkv, None, p, causal=True).reshape(B, S, E)
         x = fops.bias_dropout_add(fops.fused_dense(ctx, self.c_proj.weight, None), self.c_proj.bias, x, p)
         xn = self.ln_2(x)
@@ -81,7 +97,7 @@ class GPTBlock(nn.Module):
             t = fops.fused_dense(h, self.mlp_proj.weight, None)
         return fops.bias_dropout_add(t, self.mlp_proj.bias, x, p)
 
-    def forward_fused(self, x, xn, nxt):
+    def forward_fused(self, x, xn, nxt, rope=None):
         """The same block with its LayerNorms fused into the residual updates before them: takes the
         residual stream x and xn = ln_1(x), returns (x', nxt(x')) where nxt is the NEXT block's ln_1
         (or the final ln_f). Each residual update + the LayerNorm after it is one bdaln kernel each
@@ -90,6 +106,7 @@ class GPTBlock(nn.Module):
         B, S, E = x.shape
         p = self.p if self.training else 0.0
         qkv = fops.fused_dense(xn, self.c_attn.weight, self.c_attn.bias).view(B, S, 3, self.h, self.d)
+        qkv = self._rotate(qkv, rope)
         ctx = fops.attention_qkv_packed(qkv, None, p, causal=True).reshape(B, S, E)
         x, xn = fops.bias_dropout_add_ln(fops.fused_dense(ctx, self.c_proj.weight, None), self.c_proj.bias, x,
                                          self.ln_2.weight, self.ln_2.bias, p, self.ln_2.eps)
@@ -105,7 +122,11 @@ class GPTModel(nn.Module):
         super().__init__()
         self.config = c
         self.wte = nn.Embedding(c.padded_vocab, c.n_embd)
-        self.wpe = nn.Embedding(c.n_positions, c.n_embd)
+        self.rope = c.position_embedding_type == "rope"
+        if self.rope:
+            self.rotary_pos_emb = fused_rope.RotaryEmbedding(c.n_embd // c.n_head, c.rotary_percent, c.rotary_base)
+        else:
+            self.wpe = nn.Embedding(c.n_positions, c.n_embd)
         self.blocks = nn.ModuleList([GPTBlock(c) for _ in range(c.n_layer)])
         self.ln_f = FusedLayerNorm(c.n_embd, eps=c.layer_norm_eps)
         self.apply(self._init)
@@ -123,21 +144,26 @@ class GPTModel(nn.Module):
 
     def forward(self, input_ids, labels=None):
         B, S = input_ids.shape
-        if S > self.config.n_positions:  # host-side check: an out-of-range gather faults the GPU
-            raise ValueError(f"sequence length {S} exceeds n_positions={self.config.n_positions}")
-        pos = torch.arange(S, device=input_ids.device)
-        x = self.wte(input_ids) + self.wpe(pos)[None]
+        rope = None
+        if self.rope:
+            x = self.wte(input_ids)
+            rope = self.rotary_pos_emb.cos_sin(S, device=x.device)
+        else:
+            if S > self.config.n_positions:  # host-side check: an out-of-range gather faults the GPU
+                raise ValueError(f"sequence length {S} exceeds n_positions={self.config.n_positions}")
+            pos = torch.arange(S, device=input_ids.device)
+            x = self.wte(input_ids) + self.wpe(pos)[None]
         x = F.dropout(x, self.config.dropout, self.training)
         if len(self.blocks) and _FUSED_LN:
             # residual stream with each LayerNorm fused into the residual update before it
             xn = self.blocks[0].ln_1(x)
             for i, blk in enumerate(self.blocks):
                 nxt = self.blocks[i + 1].ln_1 if i + 1 < len(self.blocks) else self.ln_f
-                x, xn = blk.forward_fused(x, xn, nxt)
+                x, xn = blk.forward_fused(x, xn, nxt, rope)
             x = xn
         else:
             for blk in self.blocks:
-                x = blk(x)
+                x = blk(x, rope)
             x = self.ln_f(x)
         logits = fops.fused_dense(x, self.wte.weight, None)
         if labels is None:

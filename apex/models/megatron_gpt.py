@@ -26,6 +26,7 @@ from ..ops import blocks as fblocks
 from ..ops import fused as fops
 from ..transformer import parallel_state as ps
 from ..transformer import tensor_parallel as tp
+from ..transformer.functional import fused_rope
 
 
 # APEX_MEGATRON_FUSED_LN=0: per-layer forward (separate LayerNorms; A/B and fallback switch)
@@ -44,10 +45,16 @@ class MegatronGPTConfig:
     layernorm_epsilon: float = 1e-5
     init_method_std: float = 0.02
     params_dtype: torch.dtype = torch.float32
+    position_embedding_type: str = "learned"  # "learned" | "rope"
+    rotary_percent: float = 1.0
+    rotary_base: int = 10000
 
     def __post_init__(self):
         if self.ffn_hidden_size is None:
             self.ffn_hidden_size = 4 * self.hidden_size
+        if self.position_embedding_type not in ("learned", "rope"):
+            raise ValueError(f"position_embedding_type must be 'learned' or 'rope', got "
+                             f"{self.position_embedding_type!r}")
 
     @staticmethod
     def tiny():
@@ -88,12 +95,19 @@ class ParallelTransformerLayer(nn.Module):
                                                   params_dtype=c.params_dtype)
         self.p_hidden, self.p_attn = c.hidden_dropout, c.attention_dropout
 
-    def forward(self, x):
+    def _rotate(self, qkv, rope):
+        # rope = (cos, sin) [S, d2] fp32 or None (learned positions). RoPE is per head, so the
+        # rank-local heads need nothing from the TP group. No fp8 interaction: the fp8 codes-only
+        # paths live in apex.ops.blocks' whole-sublayer Functions, which this attention sublayer does
+        # not use (QKV GEMM, this rotation and the flash kernel are separate bf16 / fp16 ops).
+        return qkv if rope is None else fused_rope.apply_rotary_qkv_packed(qkv, rope[0], rope[1])
+
+    def forward(self, x, rope=None):
         B, S, _ = x.shape
         ph = self.p_hidden if self.training else 0.0
         pa = self.p_attn if self.training else 0.0
         qkv, _ = self.query_key_value(self.input_layernorm(x))
-        qkv = qkv.view(B, S, 3, self.heads_local, self.d)
+        qkv = self._rotate(qkv.view(B, S, 3, self.heads_local, self.d), rope)
         with _tp_rng():
             ctx = fops.attention_qkv_packed(qkv, None, pa, causal=True)
         out, bias = self.dense(ctx.reshape(B, S, -1))
@@ -111,7 +125,7 @@ class ParallelTransformerLayer(nn.Module):
         out, bias = f2(h)
         return fops.bias_dropout_add(out, bias, x, ph)
 
-    def forward_fused(self, x, xn, nxt):
+    def forward_fused(self, x, xn, nxt, rope=None):
         """forward() with each residual update fused with the LayerNorm after it (one bdaln kernel
         each way, fops.bias_dropout_add_ln): takes x and xn = input_layernorm(x), returns
         (x', nxt(x')) with nxt the next layer's input_layernorm / the final LayerNorm, or (x', None)
@@ -120,7 +134,7 @@ class ParallelTransformerLayer(nn.Module):
         ph = self.p_hidden if self.training else 0.0
         pa = self.p_attn if self.training else 0.0
         qkv, _ = self.query_key_value(xn)
-        qkv = qkv.view(B, S, 3, self.heads_local, self.d)
+        qkv = self._rotate(qkv.view(B, S, 3, self.heads_local, self.d), rope)
         with _tp_rng():
             ctx = fops.attention_qkv_packed(qkv, None, pa, causal=True)
         out, bias = self.dense(ctx.reshape(B, S, -1))
@@ -150,12 +164,18 @@ class MegatronGPT(nn.Module):
         self.config = c
         self.pre_process, self.post_process = pre_process, post_process
         n = c.num_layers if num_local_layers is None else num_local_layers
+        self.rope = c.position_embedding_type == "rope"
+        if self.rope:
+            # every pipeline stage builds its own tables from S (no parameters, nothing in state_dict)
+            self.rotary_pos_emb = fused_rope.RotaryEmbedding(c.hidden_size // c.num_attention_heads,
+                                                             c.rotary_percent, c.rotary_base)
         if pre_process:
             self.word_embeddings = tp.VocabParallelEmbedding(c.vocab_size, c.hidden_size,
                                                              init_method=_init(c.init_method_std),
                                                              params_dtype=c.params_dtype)
-            self.position_embeddings = nn.Embedding(c.max_position_embeddings, c.hidden_size)
-            nn.init.normal_(self.position_embeddings.weight, 0.0, c.init_method_std)
+            if not self.rope:
+                self.position_embeddings = nn.Embedding(c.max_position_embeddings, c.hidden_size)
+                nn.init.normal_(self.position_embeddings.weight, 0.0, c.init_method_std)
         self.layers = nn.ModuleList([ParallelTransformerLayer(c, layer_offset + i + 1) for i in range(n)])
         if post_process:
             self.final_layernorm = FusedLayerNorm(c.hidden_size, eps=c.layernorm_epsilon)
@@ -173,14 +193,18 @@ class MegatronGPT(nn.Module):
     def forward(self, input_ids, labels=None):
         if self.pre_process:
             S = input_ids.shape[1]
-            if S > self.config.max_position_embeddings:  # host-side check (a bad gather faults the GPU)
-                raise ValueError(f"sequence length {S} exceeds max_position_embeddings="
-                                 f"{self.config.max_position_embeddings}")
-            pos = torch.arange(S, device=input_ids.device)
-            x = self.word_embeddings(input_ids) + self.position_embeddings(pos)[None]
+            if self.rope:
+                x = self.word_embeddings(input_ids)
+            else:
+                if S > self.config.max_position_embeddings:  # host-side check (a bad gather faults the GPU)
+                    raise ValueError(f"sequence length {S} exceeds max_position_embeddings="
+                                     f"{self.config.max_position_embeddings}")
+                pos = torch.arange(S, device=input_ids.device)
+                x = self.word_embeddings(input_ids) + self.position_embeddings(pos)[None]
             x = F.dropout(x, self.config.hidden_dropout, self.training)
         else:
             x = self.input_tensor
+        rope = self.rotary_pos_emb.cos_sin(x.shape[1], device=x.device) if self.rope else None
         if _FUSED_LN and len(self.layers):
             # residual stream with each LayerNorm fused into the residual update before it
             xn = self.layers[0].input_layernorm(x)
@@ -189,12 +213,12 @@ class MegatronGPT(nn.Module):
                     nxt = self.layers[i + 1].input_layernorm
                 else:
                     nxt = self.final_layernorm if self.post_process else None
-                x, xn = layer.forward_fused(x, xn, nxt)
+                x, xn = layer.forward_fused(x, xn, nxt, rope)
             if self.post_process:
                 return self._head(xn, labels)
             return x
         for layer in self.layers:
-            x = layer(x)
+            x = layer(x, rope)
         if not self.post_process:
             return x
         return self._head(self.final_layernorm(x), labels)

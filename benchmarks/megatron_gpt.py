@@ -30,6 +30,8 @@ def main():
     ap.add_argument("--bf16-grad-accum", action="store_true",
                     help="accumulate micro-batch gradients in bf16 .grad (the pre-r3 path) instead of "
                          "the fp32 main_grad buffers")
+    ap.add_argument("--rope", action="store_true",
+                    help="rotary position embeddings (fused RoPE on packed QKV) instead of learned positions")
     args = ap.parse_args()
 
     from apex.utils.bench import emit, finish, init_distributed, instrumented_steps
@@ -59,7 +61,8 @@ def main():
     torch.manual_seed(0)
     tp.model_parallel_cuda_manual_seed(1234)
     cfg = MegatronGPTConfig(hidden_size=args.hidden, num_layers=args.layers, num_attention_heads=args.heads,
-                            max_position_embeddings=args.seq)
+                            max_position_embeddings=args.seq,
+                            position_embedding_type="rope" if args.rope else "learned")
     model = build_stage(cfg).to(env.device)
     sync_initial_embeddings(model)
     opt = FusedAdam(model.parameters(), lr=1e-4, weight_decay=0.01)
@@ -99,6 +102,7 @@ def main():
          config={"model": f"GPT {args.layers}L H{args.hidden} {args.heads} heads", "global_batch": args.global_batch,
                  "micro_batch": args.micro_batch, "seq_len": args.seq,
                  "parallelism": f"tp{args.tp}xpp{args.pp}xdp{dp}",
+                 "position_embedding": cfg.position_embedding_type,
                  "grad_accumulation": "bf16 .grad" if args.bf16_grad_accum else "fp32 main_grad"},
          extra=dict(extra, final_loss_last_stage_rank=loss))
     finish(env)

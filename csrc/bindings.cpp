@@ -1034,6 +1034,59 @@ Tensor k_smx_bwd(Tensor dy, Tensor y, double scale) {
   return dx;
 }
 
+// --------------------------------------------------------------------------
+// fused rotary position embedding: x / out are [S, B, H, D] views of any strides with D contiguous
+// (sbhd, transposed bshd, slices of packed QKV); cos / sin [rows, d2] fp32 or x's dtype.
+// Returns 1 when the 16-byte kernel ran, 0 for the scalar kernel.
+// --------------------------------------------------------------------------
+static void rope_extent(const Tensor& t, uintptr_t& lo, uintptr_t& hi) {
+  int64_t n = 1;
+  for (int i = 0; i < t.dim(); ++i) n += (t.size(i) - 1) * t.stride(i);
+  lo = reinterpret_cast<uintptr_t>(t.data_ptr());
+  hi = lo + (uintptr_t)n * t.element_size();
+}
+
+int64_t k_rope(const Tensor& x, Tensor out, const Tensor& cos, const Tensor& sin,
+               const c10::optional<Tensor>& cu_seqlens, int64_t rot_heads, bool backward) {
+  TORCH_CHECK(x.is_cuda() && out.is_cuda() && cos.is_cuda() && sin.is_cuda(), "rope: device tensors");
+  TORCH_CHECK(x.dim() == 4 && out.sizes() == x.sizes() && out.scalar_type() == x.scalar_type(),
+              "rope: x and out must be [S, B, H, D] of one dtype");
+  TORCH_CHECK(cos.dim() == 2 && sin.sizes() == cos.sizes() && sin.scalar_type() == cos.scalar_type() &&
+                  cos.is_contiguous() && sin.is_contiguous() && cos.size(0) >= 1,
+              "rope: cos / sin must be contiguous [rows, d2] tables of one dtype");
+  TORCH_CHECK(cos.scalar_type() == at::kFloat || cos.scalar_type() == x.scalar_type(),
+              "rope: tables must be fp32 or the tensor's dtype");
+  apex::RopeArgs a{};
+  a.S = x.size(0), a.B = x.size(1), a.H = x.size(2), a.D = (int)x.size(3);
+  a.rows = cos.size(0), a.d2 = (int)cos.size(1);
+  TORCH_CHECK(a.d2 % 2 == 0 && a.d2 <= a.D, "rope: d2 must be even and <= D");
+  if (x.numel() == 0) return 1;
+  TORCH_CHECK((a.D == 1 || (x.stride(3) == 1 && out.stride(3) == 1)), "rope: D must be contiguous");
+  uintptr_t xl, xh, ol, oh;
+  rope_extent(x, xl, xh);
+  rope_extent(out, ol, oh);
+  TORCH_CHECK(oh <= xl || xh <= ol, "rope: the output must not alias the input");
+  a.x = x.data_ptr(), a.y = out.data_ptr(), a.cos = cos.data_ptr(), a.sin = sin.data_ptr();
+  a.xs_s = x.stride(0), a.xs_b = x.stride(1), a.xs_h = x.stride(2);
+  a.ys_s = out.stride(0), a.ys_b = out.stride(1), a.ys_h = out.stride(2);
+  a.dt = dt_code(x.scalar_type()), a.tdt = dt_code(cos.scalar_type());
+  a.rot_heads = rot_heads < 0 ? a.H : rot_heads;
+  a.backward = backward ? 1 : 0;
+  if (cu_seqlens.has_value() && cu_seqlens->defined()) {
+    const Tensor& cu = *cu_seqlens;
+    TORCH_CHECK(cu.is_cuda() && cu.scalar_type() == at::kInt && cu.dim() == 1 && cu.is_contiguous() &&
+                    cu.numel() >= 2 && a.B == 1,
+                "rope: cu_seqlens must be a contiguous int32 device vector [nseq + 1] and t [T, 1, H, D]");
+    a.cu_seqlens = cu.data_ptr<int>();
+    a.nseq = (int)cu.numel() - 1;
+  } else {
+    TORCH_CHECK(a.rows >= a.S, "rope: the table has fewer rows than the sequence");
+  }
+  const int vec = apex::rope_vector_path(a);
+  check(apex::rope_apply(a, cur_stream()), "rope");
+  return vec;
+}
+
 // context parallelism: fused log-sum-exp merge of one ring-attention block into the fp32 accumulator
 // acc_o [B, Sa, H, D] / acc_lse [B, H, Sa] fp32 contiguous; the block o [B, S, H, D] / lse [B, H, S]
 // merges into accumulator rows s0 .. s0 + S
@@ -1580,6 +1633,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("scaled_softmax_supported", &k_smx_supported);
   m.def("scaled_masked_softmax_fwd", &k_smx_fwd);
   m.def("scaled_masked_softmax_bwd", &k_smx_bwd);
+  m.def("rope", &k_rope, py::arg("x"), py::arg("out"), py::arg("cos"), py::arg("sin"),
+        py::arg("cu_seqlens") = py::none(), py::arg("rot_heads") = -1, py::arg("backward") = false);
   m.def("bias_act_fwd", &k_bias_act_fwd);
   m.def("bias_act_bwd", &k_bias_act_bwd);
   m.def("bias_dropout_add_fwd", &k_bda_fwd);

@@ -237,6 +237,25 @@ int scaled_masked_softmax_fwd(const void* x, const uint8_t* mask, void* y, int64
 int scaled_masked_softmax_bwd(const void* dy, const void* y, void* dx, int64_t rows, int cols, float scale, int dt,
                               hipStream_t s);
 
+// ----------------------------- fused rotary position embedding (rope.hip) ---
+// x / y are [S, B, H, D] views with element strides (D contiguous, y must not overlap x); cos / sin
+// [rows, d2] contiguous in dtype tdt (fp32 or dt). Heads >= rot_heads are copied. cu_seqlens
+// (device int32 [nseq + 1], B == 1) selects thd mode: the table row is the token's offset in its
+// sequence. backward != 0 applies the transposed rotation.
+struct RopeArgs {
+  const void* x;
+  void* y;
+  const void* cos;
+  const void* sin;
+  const int* cu_seqlens;
+  int64_t S, B, H, rows;
+  int64_t xs_s, xs_b, xs_h, ys_s, ys_b, ys_h;
+  int D, d2, nseq, backward, dt, tdt;
+  int64_t rot_heads;
+};
+int rope_vector_path(const RopeArgs& a);  // 1: the 16-byte kernel applies, 0: the scalar kernel
+int rope_apply(const RopeArgs& a, hipStream_t s);
+
 // ----------------------------- softmax cross-entropy -----------------------
 int xentropy_fwd(const void* logits, const int64_t* labels, float* losses, float* lse, int64_t rows,
                  int V, float smoothing, int64_t ignore_index, int dt, hipStream_t s);
