@@ -220,23 +220,75 @@ __device__ __forceinline__ void stage_pieces(const T* __restrict__ g, int64_t ld
 #pragma unroll
   for (int j = p0; j < p0 + 2; ++j) {
     const int piece = wid * 4 + j;
-    if constexpr (TR) {
-      constexpr int LPR = 16 * (int)sizeof(T);  // lanes (16-byte chunks) per K-row: 32 (16-bit), 16 (fp8)
-      const int r = piece * (64 / LPR) + lane / LPR;
-      const int chunk = (lane % LPR) ^ (sizeof(T) == 1 ? ftr8(r) : ftr(r));
-      // partial tiles (rows % 256, e.g. GPT-2's 1600 / 4800): chunks past the last row read the
-      // last full chunk instead (rows % 8 == 0) — they only feed output rows / columns the
-      // bounds-checked epilogue does not store, and the last K-row never reads past the tensor
-      int col = row0 + chunk * (16 / (int)sizeof(T));
-      col = col < rows ? col : rows - 16 / (int)sizeof(T);
-      glds16(g + (int64_t)(k0 + r) * ld + col, lds_tile + piece * 1024);
-    } else {
-      const int r = piece * 8 + (lane >> 3);
-      const int chunk = (lane & 7) ^ ((r >> 1) & 7);
-      int gr = row0 + r;
-      gr = gr < rows ? gr : rows - 1;
-      glds16(g + (int64_t)gr * ld + k0 + chunk * (16 / (int)sizeof(T)), lds_tile + piece * 1024);
-    }
+    static_assert(!TR, "TR = true stages through TrSrc (below)");
+    const int r = piece * 8 + (lane >> 3);
+    const int chunk = (lane & 7) ^ ((r >> 1) & 7);
+    int gr = row0 + r;
+    gr = gr < rows ? gr : rows - 1;
+    glds16(g + (int64_t)gr * ld + k0 + chunk * (16 / (int)sizeof(T)), lds_tile + piece * 1024);
+  }
+}
+
+// TR = true staging: lane l of piece p reads g + (k0 + r) * ld + col, r = the piece's K-row of the lane,
+// col = the swizzled chunk's first column. Only k0 changes over the K loop and it is wave-uniform, so the
+// address is split and the loop carries no per-lane address math (formed whole per load it cost seven
+// VALU, three of them 32-bit multiplies, for each of the 16 loads of a K-tile pair, all in the R sections
+// the other wave group's MFMA phase has to cover):
+//   off[j]  per lane, loop invariant: byte offset of piece j's 16-byte chunk from the first K-row this
+//           wave stages in a K-tile — the K-row inside the wave's four pieces, the swizzled chunk column
+//           and the partial-tile clamp. 32 bits: gemm_tt*_supported bound ld so that the wave's 8
+//           (fp8: 16) K-rows span less than 4 GiB.
+//   base    wave-uniform 64-bit address of that K-row in the K-tile staged last: SGPRs, the saddr form of
+//           global_load_lds, advanced by `step` bytes with scalar adds (operands past 4 GiB: nothing
+//           running is 32 bits wide). It moves only when the next K-tile exists, so no address outside
+//           [g, g + K * ld) is ever formed.
+template <typename T>
+struct TrSrc {
+  const char* base;
+  int64_t step;
+  uint32_t off[4];
+};
+template <typename T>
+__device__ __forceinline__ TrSrc<T> tr_src(const T* __restrict__ g, int64_t ld, int row0, int rows, int wid, int lane) {
+  constexpr int ES = (int)sizeof(T), LPR = 16 * ES, RPP = 64 / LPR;  // K-rows per piece: 2 (16-bit), 4 (fp8)
+  TrSrc<T> s;
+  s.base = reinterpret_cast<const char*>(g + (int64_t)(wid * 4 * RPP) * ld);
+  s.step = (int64_t)(128 / ES) * ld * ES;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int r = (wid * 4 + j) * RPP + lane / LPR;
+    const int chunk = (lane % LPR) ^ (ES == 1 ? ftr8(r) : ftr(r));
+    // partial tiles (rows % 256, e.g. GPT-2's 1600 / 4800): chunks past the last row read the
+    // last full chunk instead (rows % 8 == 0) — they only feed output rows / columns the
+    // bounds-checked epilogue does not store, and the last K-row never reads past the tensor
+    int col = row0 + chunk * (16 / ES);
+    col = col < rows ? col : rows - 16 / ES;
+    s.off[j] = ((uint32_t)(j * RPP + lane / LPR) * (uint32_t)ld + (uint32_t)col) * (uint32_t)ES;
+  }
+  return s;
+}
+template <typename T>
+__device__ __forceinline__ void stage_tr(const TrSrc<T>& s, char* lds_tile, int wid, int p0) {
+#pragma unroll
+  for (int j = p0; j < p0 + 2; ++j) {
+    // kept opaque so that the zero-extension stays in the block of the load: hoisted out of the K loop,
+    // hipcc carries each offset as a 64-bit VGPR pair and adds the base per lane (v_lshl_add_u64)
+    // instead of selecting the saddr form
+    uint32_t o = s.off[j];
+    asm volatile("" : "+v"(o));
+    glds16(s.base + o, lds_tile + (wid * 4 + j) * 1024);
+  }
+}
+// One K-loop staging step: stage_pieces for TR = false (ts unused); for TR the operand's TrSrc, moved to
+// the next K-tile first when `adv` (the first two of its four pieces)
+template <typename T, bool TR>
+__device__ __forceinline__ void stage_k(const T* __restrict__ g, int64_t ld, int row0, int rows, int k0, char* lds_tile,
+                                        int wid, int lane, int p0, TrSrc<T>* ts, bool adv) {
+  if constexpr (TR) {
+    if (adv) ts->base += ts->step;
+    stage_tr(*ts, lds_tile, wid, p0);
+  } else {
+    stage_pieces<T, false>(g, ld, row0, rows, k0, lds_tile, wid, lane, p0);
   }
 }
 
@@ -311,7 +363,8 @@ __device__ __forceinline__ s16x8 frag(const char* tile, int rb, int s, int lr, i
 template <typename T, bool TR, int FA, int FB, int DBG, bool FRESH = false>
 __device__ __forceinline__ void mainloop_bk64_loop(const T* __restrict__ A, const T* __restrict__ B, int M, int N,
                                                    int K, int64_t lda, int64_t ldb, int m0, int n0, char* smem,
-                                                   int wid, int wr, int wc, int lane, f32x4 (&acc)[4][8]);
+                                                   int wid, int wr, int wc, int lane, f32x4 (&acc)[4][8],
+                                                   TrSrc<T>* ts = nullptr);
 template <typename T, bool TR, int FA = -1, int FB = -1, int DBG = 0>
 __device__ __forceinline__ void mainloop_bk64(const T* __restrict__ A, const T* __restrict__ B, int M, int N, int K,
                                               int64_t lda, int64_t ldb, int m0, int n0, char* smem, int wid, int wr,
@@ -322,20 +375,25 @@ __device__ __forceinline__ void mainloop_bk64(const T* __restrict__ A, const T* 
   constexpr int BKE = 128 / (int)sizeof(T);
   const int nt = K / BKE;
   // prologue: A(0), B(0) -> buf0, B(1) -> buf1; retire tile 0
-  stage_pieces<T, TR>(A, lda, m0, M, 0, smem, wid, lane, 0);
-  stage_pieces<T, TR>(A, lda, m0, M, 0, smem, wid, lane, 2);
-  stage_pieces<T, TR>(B, ldb, n0, N, 0, smem + G_TILE_BYTES, wid, lane, 0);
-  stage_pieces<T, TR>(B, ldb, n0, N, 0, smem + G_TILE_BYTES, wid, lane, 2);
+  TrSrc<T> ts[2];
+  if constexpr (TR) {
+    ts[0] = tr_src<T>(A, lda, m0, M, wid, lane);
+    ts[1] = tr_src<T>(B, ldb, n0, N, wid, lane);
+  }
+  stage_k<T, TR>(A, lda, m0, M, 0, smem, wid, lane, 0, &ts[0], false);
+  stage_k<T, TR>(A, lda, m0, M, 0, smem, wid, lane, 2, &ts[0], false);
+  stage_k<T, TR>(B, ldb, n0, N, 0, smem + G_TILE_BYTES, wid, lane, 0, &ts[1], false);
+  stage_k<T, TR>(B, ldb, n0, N, 0, smem + G_TILE_BYTES, wid, lane, 2, &ts[1], false);
   if (nt > 1) {
-    stage_pieces<T, TR>(B, ldb, n0, N, BKE, smem + G_BUF_BYTES + G_TILE_BYTES, wid, lane, 0);
-    stage_pieces<T, TR>(B, ldb, n0, N, BKE, smem + G_BUF_BYTES + G_TILE_BYTES, wid, lane, 2);
+    stage_k<T, TR>(B, ldb, n0, N, BKE, smem + G_BUF_BYTES + G_TILE_BYTES, wid, lane, 0, &ts[1], true);
+    stage_k<T, TR>(B, ldb, n0, N, BKE, smem + G_BUF_BYTES + G_TILE_BYTES, wid, lane, 2, &ts[1], false);
     asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
   } else {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   bar();
   if (wr == 1) bar();  // stagger group 1 by one barrier
-  mainloop_bk64_loop<T, TR, FA, FB, DBG>(A, B, M, N, K, lda, ldb, m0, n0, smem, wid, wr, wc, lane, acc);
+  mainloop_bk64_loop<T, TR, FA, FB, DBG>(A, B, M, N, K, lda, ldb, m0, n0, smem, wid, wr, wc, lane, acc, ts);
 }
 
 // mainloop_bk64's K loop (tile 0 staged and retired, the wave groups staggered): also the fp8 body of
@@ -345,7 +403,8 @@ __device__ __forceinline__ void mainloop_bk64(const T* __restrict__ A, const T* 
 template <typename T, bool TR, int FA, int FB, int DBG, bool FRESH>
 __device__ __forceinline__ void mainloop_bk64_loop(const T* __restrict__ A, const T* __restrict__ B, int M, int N,
                                                    int K, int64_t lda, int64_t ldb, int m0, int n0, char* smem,
-                                                   int wid, int wr, int wc, int lane_in, f32x4 (&acc)[4][8]) {
+                                                   int wid, int wr, int wc, int lane_in, f32x4 (&acc)[4][8],
+                                                   TrSrc<T>* ts) {
   constexpr bool F8 = FA >= 0;
   constexpr int BKE = 128 / (int)sizeof(T);
   const int nt = K / BKE;
@@ -365,7 +424,7 @@ __device__ __forceinline__ void mainloop_bk64_loop(const T* __restrict__ A, cons
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       if constexpr (!(DBG & 128)) for (int s = 0; s < 2; ++s) fa[i][s] = frag<TR, sizeof(T)>(ta, wr * 128 + i * 16, s, lr, lk);
-    if (ld_a && !(DBG & 32)) stage_pieces<T, TR>(A, lda, m0, M, (t + 1) * BKE, oth, wid, lane, 0);
+    if (ld_a && !(DBG & 32)) stage_k<T, TR>(A, lda, m0, M, (t + 1) * BKE, oth, wid, lane, 0, &ts[0], true);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if constexpr (!(DBG & 64)) bar();
     __builtin_amdgcn_s_setprio(1);
@@ -388,7 +447,7 @@ __device__ __forceinline__ void mainloop_bk64_loop(const T* __restrict__ A, cons
 #pragma unroll
     for (int j = 0; j < 2; ++j)
       if constexpr (!(DBG & 128)) for (int s = 0; s < 2; ++s) fb1[j][s] = frag<TR, sizeof(T)>(tb, wc * 64 + 32 + j * 16, s, lr, lk);
-    if (ld_a && !(DBG & 32)) stage_pieces<T, TR>(A, lda, m0, M, (t + 1) * BKE, oth, wid, lane, 2);
+    if (ld_a && !(DBG & 32)) stage_k<T, TR>(A, lda, m0, M, (t + 1) * BKE, oth, wid, lane, 2, &ts[0], false);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if constexpr (!(DBG & 64)) bar();
     __builtin_amdgcn_s_setprio(1);
@@ -411,7 +470,7 @@ __device__ __forceinline__ void mainloop_bk64_loop(const T* __restrict__ A, cons
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       if constexpr (!(DBG & 128)) for (int s = 0; s < 2; ++s) fa[i][s] = frag<TR, sizeof(T)>(ta, wr * 128 + 64 + i * 16, s, lr, lk);
-    if (ld_b && !(DBG & 32)) stage_pieces<T, TR>(B, ldb, n0, N, (t + 2) * BKE, cur + G_TILE_BYTES, wid, lane, 0);
+    if (ld_b && !(DBG & 32)) stage_k<T, TR>(B, ldb, n0, N, (t + 2) * BKE, cur + G_TILE_BYTES, wid, lane, 0, &ts[1], true);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if constexpr (!(DBG & 64)) bar();
     __builtin_amdgcn_s_setprio(1);
@@ -432,7 +491,7 @@ __device__ __forceinline__ void mainloop_bk64_loop(const T* __restrict__ A, cons
     if constexpr (!(DBG & 64)) bar();
     // ---------------- p4: stage B(t+2) pieces 2,3; retire A(t+1), B(t+1) ----------------
     if (ld_b) {
-      if constexpr (!(DBG & 32)) stage_pieces<T, TR>(B, ldb, n0, N, (t + 2) * BKE, cur + G_TILE_BYTES, wid, lane, 2);
+      if constexpr (!(DBG & 32)) stage_k<T, TR>(B, ldb, n0, N, (t + 2) * BKE, cur + G_TILE_BYTES, wid, lane, 2, &ts[1], false);
       asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -508,7 +567,8 @@ __device__ __forceinline__ void quad_mma(f32x4 (&acc)[4][8], const s16x8 (&fa)[4
 template <typename T, bool TR, int FA, int FB, int DBG, int PAR>
 __device__ __forceinline__ void bal_tile(int t, int nt, const T* __restrict__ A, const T* __restrict__ B, int M, int N,
                                          int64_t lda, int64_t ldb, int m0, int n0, char* smem, int wid, int wr, int wc,
-                                         int lane, f32x4 (&acc)[4][8], s16x8 (&fa)[4][2], s16x8 (&fb)[2][2][2]) {
+                                         int lane, f32x4 (&acc)[4][8], s16x8 (&fa)[4][2], s16x8 (&fb)[2][2][2],
+                                         TrSrc<T>* ts = nullptr) {
   constexpr int BKE = 128 / (int)sizeof(T);
   constexpr int OP = 1 - PAR;
   const int lr = lane & 15, lk = lane >> 4;
@@ -524,14 +584,14 @@ __device__ __forceinline__ void bal_tile(int t, int nt, const T* __restrict__ A,
   constexpr bool RD = !(DBG & 128), GL = !(DBG & 32), BR = !(DBG & 64);
   // p1: A rows mh=0; stage A(t+1) pieces 0,1
   if constexpr (RD) read_fa<TR, sizeof(T)>(fa, ta, wr * 128, lr, lk);
-  if (GL && ld_a) stage_pieces<T, TR>(A, lda, m0, M, (t + 1) * BKE, oth, wid, lane, 0);
+  if (GL && ld_a) stage_k<T, TR>(A, lda, m0, M, (t + 1) * BKE, oth, wid, lane, 0, &ts[0], true);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   if constexpr (BR) bar();
   quad_mma<T, FA, FB, 0, PAR>(acc, fa, fb[PAR]);
   if constexpr (BR) bar();
   // p2: B half OP; stage A(t+1) pieces 2,3
   if constexpr (RD) read_fb<TR, sizeof(T)>(fb[OP], tb, wc * 64 + OP * 32, lr, lk);
-  if (GL && ld_a) stage_pieces<T, TR>(A, lda, m0, M, (t + 1) * BKE, oth, wid, lane, 2);
+  if (GL && ld_a) stage_k<T, TR>(A, lda, m0, M, (t + 1) * BKE, oth, wid, lane, 2, &ts[0], false);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   if constexpr (BR) bar();
   quad_mma<T, FA, FB, 0, OP>(acc, fa, fb[OP]);
@@ -539,7 +599,7 @@ __device__ __forceinline__ void bal_tile(int t, int nt, const T* __restrict__ A,
   // p3: A rows mh=1; stage B(t+2) pieces 0,1 into this buffer; retire B(t+1) for p4
   if constexpr (RD) read_fa<TR, sizeof(T)>(fa, ta, wr * 128 + 64, lr, lk);
   if (ld_b) {
-    if constexpr (GL) stage_pieces<T, TR>(B, ldb, n0, N, (t + 2) * BKE, cur + G_TILE_BYTES, wid, lane, 0);
+    if constexpr (GL) stage_k<T, TR>(B, ldb, n0, N, (t + 2) * BKE, cur + G_TILE_BYTES, wid, lane, 0, &ts[1], true);
     asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
   } else if (ld_a) {
     asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -553,7 +613,7 @@ __device__ __forceinline__ void bal_tile(int t, int nt, const T* __restrict__ A,
   // would keep the old fragment live across the phase and cost registers.)
   if constexpr (RD) read_fb<TR, sizeof(T)>(fb[OP], oth + G_TILE_BYTES, wc * 64 + OP * 32, lr, lk);
   if (ld_b) {
-    if constexpr (GL) stage_pieces<T, TR>(B, ldb, n0, N, (t + 2) * BKE, cur + G_TILE_BYTES, wid, lane, 2);
+    if constexpr (GL) stage_k<T, TR>(B, ldb, n0, N, (t + 2) * BKE, cur + G_TILE_BYTES, wid, lane, 2, &ts[1], false);
     asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
   } else {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -570,13 +630,18 @@ __device__ __forceinline__ void mainloop_bal(const T* __restrict__ A, const T* _
                                              int wc, int lane, f32x4 (&acc)[4][8]) {
   constexpr int BKE = 128 / (int)sizeof(T);
   const int nt = K / BKE;
-  stage_pieces<T, TR>(A, lda, m0, M, 0, smem, wid, lane, 0);
-  stage_pieces<T, TR>(A, lda, m0, M, 0, smem, wid, lane, 2);
-  stage_pieces<T, TR>(B, ldb, n0, N, 0, smem + G_TILE_BYTES, wid, lane, 0);
-  stage_pieces<T, TR>(B, ldb, n0, N, 0, smem + G_TILE_BYTES, wid, lane, 2);
+  TrSrc<T> ts[2];
+  if constexpr (TR) {
+    ts[0] = tr_src<T>(A, lda, m0, M, wid, lane);
+    ts[1] = tr_src<T>(B, ldb, n0, N, wid, lane);
+  }
+  stage_k<T, TR>(A, lda, m0, M, 0, smem, wid, lane, 0, &ts[0], false);
+  stage_k<T, TR>(A, lda, m0, M, 0, smem, wid, lane, 2, &ts[0], false);
+  stage_k<T, TR>(B, ldb, n0, N, 0, smem + G_TILE_BYTES, wid, lane, 0, &ts[1], false);
+  stage_k<T, TR>(B, ldb, n0, N, 0, smem + G_TILE_BYTES, wid, lane, 2, &ts[1], false);
   if (nt > 1) {
-    stage_pieces<T, TR>(B, ldb, n0, N, BKE, smem + G_BUF_BYTES + G_TILE_BYTES, wid, lane, 0);
-    stage_pieces<T, TR>(B, ldb, n0, N, BKE, smem + G_BUF_BYTES + G_TILE_BYTES, wid, lane, 2);
+    stage_k<T, TR>(B, ldb, n0, N, BKE, smem + G_BUF_BYTES + G_TILE_BYTES, wid, lane, 0, &ts[1], true);
+    stage_k<T, TR>(B, ldb, n0, N, BKE, smem + G_BUF_BYTES + G_TILE_BYTES, wid, lane, 2, &ts[1], false);
     asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
   } else {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -588,10 +653,10 @@ __device__ __forceinline__ void mainloop_bal(const T* __restrict__ A, const T* _
   if constexpr (!(DBG & 128)) read_fb<TR, sizeof(T)>(fb[0], smem + G_TILE_BYTES, wc * 64, lr, lk);  // tile 0's first B half
   int t = 0;
   for (; t + 1 < nt; t += 2) {
-    bal_tile<T, TR, FA, FB, DBG, 0>(t, nt, A, B, M, N, lda, ldb, m0, n0, smem, wid, wr, wc, lane, acc, fa, fb);
-    bal_tile<T, TR, FA, FB, DBG, 1>(t + 1, nt, A, B, M, N, lda, ldb, m0, n0, smem, wid, wr, wc, lane, acc, fa, fb);
+    bal_tile<T, TR, FA, FB, DBG, 0>(t, nt, A, B, M, N, lda, ldb, m0, n0, smem, wid, wr, wc, lane, acc, fa, fb, ts);
+    bal_tile<T, TR, FA, FB, DBG, 1>(t + 1, nt, A, B, M, N, lda, ldb, m0, n0, smem, wid, wr, wc, lane, acc, fa, fb, ts);
   }
-  if (t < nt) bal_tile<T, TR, FA, FB, DBG, 0>(t, nt, A, B, M, N, lda, ldb, m0, n0, smem, wid, wr, wc, lane, acc, fa, fb);
+  if (t < nt) bal_tile<T, TR, FA, FB, DBG, 0>(t, nt, A, B, M, N, lda, ldb, m0, n0, smem, wid, wr, wc, lane, acc, fa, fb, ts);
 }
 
 // Buffer resource for a wave-uniform base address (the epilogue's full-tile path): every lane
@@ -1666,9 +1731,10 @@ int gemm_nt_f8(const GemmArgs& g, int fmt_a, int fmt_b, int out_dt, hipStream_t 
 }
 
 bool gemm_tt_supported(int P, int Q, int R, int splits, int64_t lda, int64_t ldb) {
-  // P, Q: any multiple of 8 (partial 256-tiles: clamped staging + bounds-checked epilogues)
+  // P, Q: any multiple of 8 (partial 256-tiles: clamped staging + bounds-checked epilogues);
+  // ld < 2^28: TrSrc's 32-bit per-lane offsets span the 8 K-rows a wave stages
   return P > 0 && Q > 0 && splits > 0 && P % 8 == 0 && Q % 8 == 0 && R % GB_K == 0 && R / GB_K >= splits &&
-         lda % 8 == 0 && ldb % 8 == 0;
+         lda % 8 == 0 && ldb % 8 == 0 && lda >= P && ldb >= Q && lda < (1 << 28) && ldb < (1 << 28);
 }
 
 int gemm_tt(const GemmArgs& g, int dt, hipStream_t s) {
@@ -1693,9 +1759,10 @@ int gemm_tt(const GemmArgs& g, int dt, hipStream_t s) {
 }
 
 bool gemm_tt_f8_supported(int P, int Q, int R, int splits, int64_t lda, int64_t ldb) {
-  // fp8 codes: 16-byte chunks of 16 columns (partial 256-tiles clamp to the last full chunk)
+  // fp8 codes: 16-byte chunks of 16 columns (partial 256-tiles clamp to the last full chunk);
+  // ld < 2^28: TrSrc's 32-bit per-lane offsets span the 16 K-rows a wave stages
   return P > 0 && Q > 0 && splits > 0 && P % 16 == 0 && Q % 16 == 0 && R % 128 == 0 && R / 128 >= splits &&
-         lda % 16 == 0 && ldb % 16 == 0;
+         lda % 16 == 0 && ldb % 16 == 0 && lda >= P && ldb >= Q && lda < (1 << 28) && ldb < (1 << 28);
 }
 
 // fp8 weight gradient: fp32 slabs [splits, P, Q] of alpha_a alpha_b sum_r A[r, p] B[r, q] over the
