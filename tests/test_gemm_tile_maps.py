@@ -1,4 +1,4 @@
-"""Host models of the GEMM kernels' workgroup -> tile maps (csrc/gemm.hip), checked exhaustively on
+"""Host models of the GEMM kernels' workgroup -> tile maps (csrc/gemm_kernels.h), checked exhaustively on
 the CPU: every launch must visit each (tile, K-slice) exactly once whatever the tile count, slice
 count or grid, or a tile is silently lost / computed twice. The formulas below are the device code's,
 line for line:
@@ -16,7 +16,7 @@ G_GROUP_M = 8
 
 
 def xcd_remap(v, n):
-    """the bijective XCD remap of csrc/gemm.hip: virtual id v of n -> contiguous range per XCD"""
+    """the bijective XCD remap of csrc/gemm_kernels.h: virtual id v of n -> contiguous range per XCD"""
     xcd, q, rr = v & 7, n >> 3, n & 7
     return (xcd * (q + 1) if xcd < rr else rr * (q + 1) + (xcd - rr) * q) + (v >> 3)
 

@@ -4,8 +4,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Icsrc tools/gemmlab/lab.hip -o build/gemmlab
 //   build/gemmlab M N K [epi=0] [rounds=5] [reps=10]
 // Prints one JSON line per variant: us per call (min / median over rounds), PF/s, max |diff|.
-#include "../../csrc/gemm.hip"
-#include "lab_variants.h"
+#include "lab_variants.h"  // (the production kernels too: csrc/gemm_kernels.h)
 
 #include <hip/hip_runtime.h>
 
@@ -77,12 +76,12 @@ void launch_old(const Bufs& b, hipStream_t s) {
                        b.M, b.N, b.K, (int64_t)b.K, (int64_t)b.K, (int64_t)b.N, b.bias, b.aux, (int64_t)b.N, b.aux_out, b.part,
                        STAGGER, nullptr, nullptr);
 }
-// timeline trace (LAB_TRACE): the production kernel with DBG bit 2048, 4 x uint64 per workgroup
+// timeline trace (LAB_TRACE): the production kernel with kLabTrace, 4 x uint64 per workgroup
 uint64_t* g_trace = nullptr;
 template <int EPI>
 void launch_trace(const Bufs& b, hipStream_t s) {
   const int tiles = ((b.M + 255) / 256) * ((b.N + 255) / 256);
-  hipLaunchKernelGGL((gemm_nt_kernel<bf16, EPI, false, false, bf16, -1, -1, 2048>), dim3(tiles), dim3(512), 0, s, b.A, b.B,
+  hipLaunchKernelGGL((gemm_nt_kernel<bf16, EPI, false, false, bf16, -1, -1, kLabTrace>), dim3(tiles), dim3(512), 0, s, b.A, b.B,
                      b.C, b.M, b.N, b.K, (int64_t)b.K, (int64_t)b.K, (int64_t)b.N, b.bias, b.aux, (int64_t)b.N, b.aux_out,
                      b.part, 0, (const float*)g_trace, nullptr);
 }
@@ -198,26 +197,26 @@ void run_epi(Bufs& b, int rounds, int reps, hipStream_t s) {
     const char* name;
     void (*fn)(const Bufs&, hipStream_t);
   };
-  std::vector<V> vs = {{"w8", launch_old<EPI>}, {"w8old", launch_old<EPI, 1024>}};
+  std::vector<V> vs = {{"w8", launch_old<EPI>}, {"w8old", launch_old<EPI, kLabOldLoop>}};
   // the other variants have no bounds-checked form: full tiles only
   const bool full = b.M % 256 == 0 && b.N % 256 == 0;
   if (full && getenv("LAB_W8P")) vs.push_back({"w8p", launch_w8p<EPI>});
   if (full && getenv("LAB_M32")) vs.push_back({"w8m32", launch_m32<EPI>});
   if (full && getenv("LAB_W2G")) vs.push_back({"w2g", launch_w2g<EPI>});
   if (full && getenv("LAB_NOEPI")) {
-    vs.push_back({"w8_noepi", launch_old<EPI, 512>});
-    vs.push_back({"w8p_noepi", launch_w8p<EPI, 512>});
+    vs.push_back({"w8_noepi", launch_old<EPI, kLabNoEpilogue>});
+    vs.push_back({"w8p_noepi", launch_w8p<EPI, kLabNoEpilogue>});
   }
   if (full && getenv("LAB_W4")) {
     vs.push_back({"w4", launch_w4<EPI>});
     vs.push_back({"w4r", launch_w4<EPI, 256>});
   }
   if (full && getenv("LAB_DBG")) {
-    vs.push_back({"w8_noglds", launch_old<EPI, 32>});
-    vs.push_back({"w8_nobar", launch_old<EPI, 64>});
-    vs.push_back({"w8_nodsread", launch_old<EPI, 128>});
-    vs.push_back({"w8_nomem", launch_old<EPI, 32 + 64 + 128>});
-    vs.push_back({"w8_noepi", launch_old<EPI, 512>});
+    vs.push_back({"w8_noglds", launch_old<EPI, kLabNoGlds>});
+    vs.push_back({"w8_nobar", launch_old<EPI, kLabNoBarrier>});
+    vs.push_back({"w8_nodsread", launch_old<EPI, kLabNoDsRead>});
+    vs.push_back({"w8_nomem", launch_old<EPI, kLabNoGlds + kLabNoBarrier + kLabNoDsRead>});
+    vs.push_back({"w8_noepi", launch_old<EPI, kLabNoEpilogue>});
   }
   if (full && getenv("LAB_STAGGER")) {
     vs.push_back({"w8_st1", launch_old<EPI, 0, 1>});
@@ -227,18 +226,13 @@ void run_epi(Bufs& b, int rounds, int reps, hipStream_t s) {
   }
   if (full && getenv("LAB_TRACE")) {
     trace_summary(b, EPI, s, launch_trace<EPI>);
-    trace_summary(b, EPI, s, launch_persist<EPI, 2048>);
+    trace_summary(b, EPI, s, launch_persist<EPI, kLabTrace>);
   }
   if (full && !getenv("LAB_NOPERSIST")) vs.push_back({"w8pers", launch_persist<EPI>});
   if (full && getenv("LAB_PXD")) {  // persistent-kernel epilogue diagnostics (epilogue XD bits)
-    vs.push_back({"pers_nomath", launch_persist<EPI, 4096>});
-    vs.push_back({"pers_nostore", launch_persist<EPI, 8192>});
-    vs.push_back({"pers_nomath_nostore", launch_persist<EPI, 12288>});
-  }
-  if (full && getenv("LAB_NT")) {  // non-temporal epilogue stores (XD bits 2, 3)
-    vs.push_back({"pers_nt_aux", launch_persist<EPI, 16384>});
-    vs.push_back({"pers_nt_c", launch_persist<EPI, 32768>});
-    vs.push_back({"pers_nt_both", launch_persist<EPI, 49152>});
+    vs.push_back({"pers_nomath", launch_persist<EPI, kEpiNoMath << kLabEpiShift>});
+    vs.push_back({"pers_nostore", launch_persist<EPI, kEpiNoStore << kLabEpiShift>});
+    vs.push_back({"pers_nomath_nostore", launch_persist<EPI, (kEpiNoMath | kEpiNoStore) << kLabEpiShift>});
   }
   const int64_t MN = (int64_t)b.M * b.N;
   float* dmax;

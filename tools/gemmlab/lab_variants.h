@@ -1,9 +1,11 @@
 // Lab-only GEMM variants (measured negatives, kept for A/B in tools/gemmlab/lab.hip; never part of the
 // production extension): the four-wave 128x128-wave-tile kernel (w4 / w4r), the two-workgroup
 // 256x128 kernel (w2g), the 32x32x16-fragment kernel (m32) and the per-wave software-pipelined kernel
-// (w8p). Results and reasons they lost are in profiles/README.md (rounds 3-4). Included by lab.hip
-// right after csrc/gemm.hip, inside the same anonymous namespace.
+// (w8p). Results and reasons they lost are in profiles/README.md (rounds 3-4). Built on the
+// production kernels' pieces (csrc/gemm_kernels.h), inside the same anonymous namespace; DBG takes the
+// kLab* switches of csrc/gemm_mainloop.h plus this file's own bits (1 .. 16, 256).
 #pragma once
+#include "../../csrc/gemm_kernels.h"
 namespace apex {
 namespace {
 // ============================================================================================
@@ -128,7 +130,7 @@ __device__ __forceinline__ void mainloop_w4(__amdgpu_buffer_rsrc_t rsa, __amdgpu
     }
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-      if constexpr (!(DBG & 128)) read1(cur, 1, q, fa1, fb1);
+      if constexpr (!(DBG & kLabNoDsRead)) read1(cur, 1, q, fa1, fb1);
       if constexpr (DBG & 8) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -146,12 +148,12 @@ __device__ __forceinline__ void mainloop_w4(__amdgpu_buffer_rsrc_t rsa, __amdgpu
       mma1(fa1, fb1, l);
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    if constexpr (!(DBG & 64)) bar();
+    if constexpr (!(DBG & kLabNoBarrier)) bar();
     // s = 1, rows 4..7: next tile's first fragments + the tile-after-next's LDS-DMA pieces
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-      if constexpr (NEXT && !(DBG & 128)) read1(nxt, 0, q, fa0, fb0);
-      if constexpr (STAGE && !(DBG & 32)) stage1(t + 2, t & 1, q);
+      if constexpr (NEXT && !(DBG & kLabNoDsRead)) read1(nxt, 0, q, fa0, fb0);
+      if constexpr (STAGE && !(DBG & kLabNoGlds)) stage1(t + 2, t & 1, q);
       if constexpr (DBG & 8) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -321,7 +323,7 @@ __global__ void __launch_bounds__(W_THREADS, 1) gemm_w4_kernel(const T* __restri
     }
     return;
   }
-  if constexpr (DBG & 512) {  // keep the accumulators live, store nothing
+  if constexpr (DBG & kLabNoEpilogue) {  // keep the accumulators live, store nothing
     float t = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j)
@@ -657,7 +659,7 @@ __global__ void __launch_bounds__(G_THREADS) gemm_m32_kernel(const T* __restrict
   mainloop_m32<T>(A, B, M, N, K, lda, ldb, m0, n0, smem, wid, wr, wc, lane, acc);
   if (wr == 0) bar();
   bar();
-  if constexpr (DBG & 512) {  // keep the accumulators live, store nothing
+  if constexpr (DBG & kLabNoEpilogue) {  // keep the accumulators live, store nothing
     float t = 0.f;
 #pragma unroll
     for (int j = 0; j < 2; ++j)
@@ -820,7 +822,7 @@ __global__ void __launch_bounds__(G_THREADS) gemm_w8p_kernel(const T* __restrict
     for (int i = 0; i < 8; ++i) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
   mainloop_w8p<T>(A, B, M, N, K, lda, ldb, m0, n0, smem, wid, wr, wc, lane, acc);
   bar();  // every wave is past its last ds_read: LDS is free for the epilogue
-  if constexpr (DBG & 512) {
+  if constexpr (DBG & kLabNoEpilogue) {
     float t = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j)

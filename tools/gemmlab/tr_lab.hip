@@ -9,12 +9,12 @@
 //   tr_noepi     main loop only (accumulators kept live, nothing stored)
 //   tr_nodsread  ... and no fragment ds_reads
 //   tr_noglds    ... and no global->LDS copies (main loop: barriers + ds_reads + MFMAs)
-//   *_old        the same with the previous main loop (mainloop_bk64, DBG bit 1024; production is
+//   *_old        the same with the previous main loop (mainloop_bk64, kLabOldLoop; production is
 //                mainloop_bal); its fp32 slabs are compared with production's (max |diff|, "maxdiff")
 //   nt_f32 / nt_noepi   the NT kernel on [P*splits, R/splits] x [Q, R/splits] (same tiles, same
 //                per-tile K, operands K-contiguous)
 // One JSON line per variant: us per call (min / median over rounds), PF/s.
-#include "../../csrc/gemm.hip"
+#include "lab_variants.h"  // (the production kernels too: csrc/gemm_kernels.h)
 
 #include <hip/hip_runtime.h>
 
@@ -120,15 +120,15 @@ int main(int argc, char** argv) {
   std::vector<V> vs = {{"tr_f32", tr<EPI_F32, 0>},
                        {"tr_w4_f32", tr_w4<EPI_F32, 0>},
                        {"tr_w4r_f32", tr_w4<EPI_F32, 256>},
-                       {"tr_f32_old", tr<EPI_F32, 1024>},
-                       {"tr_noepi", tr<EPI_NONE, 512>},
-                       {"tr_noepi_old", tr<EPI_NONE, 512 + 1024>},
-                       {"tr_nodsread", tr<EPI_NONE, 512 + 128>},
-                       {"tr_noglds", tr<EPI_NONE, 512 + 32>},
+                       {"tr_f32_old", tr<EPI_F32, kLabOldLoop>},
+                       {"tr_noepi", tr<EPI_NONE, kLabNoEpilogue>},
+                       {"tr_noepi_old", tr<EPI_NONE, kLabNoEpilogue + kLabOldLoop>},
+                       {"tr_nodsread", tr<EPI_NONE, kLabNoEpilogue + kLabNoDsRead>},
+                       {"tr_noglds", tr<EPI_NONE, kLabNoEpilogue + kLabNoGlds>},
                        {"nt_f32", nt<EPI_F32, 0>},
-                       {"nt_f32_old", nt<EPI_F32, 1024>},
-                       {"nt_noepi", nt<EPI_NONE, 512>},
-                       {"nt_nodsread", nt<EPI_NONE, 512 + 128>}};
+                       {"nt_f32_old", nt<EPI_F32, kLabOldLoop>},
+                       {"nt_noepi", nt<EPI_NONE, kLabNoEpilogue>},
+                       {"nt_nodsread", nt<EPI_NONE, kLabNoEpilogue + kLabNoDsRead>}};
   // correctness: each *_f32_old slab set against the production loop's
   const int64_t nP = (int64_t)p.S * p.P * p.Q;
   float *ref, *dmax;
