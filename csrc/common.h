@@ -229,7 +229,20 @@ __device__ __forceinline__ float u32_to_unit(uint32_t x) {
 
 }  // namespace apex
 
-#define APEX_HIP_CHECK(expr)                                                    \
+// Host-side launchers: run the statement with T bound to the element type of dtype code DT
+// (16-bit-only attention has its own ATTN_DISPATCH), or with a constexpr bool NAME bound to X.
+#define APEX_DISPATCH_T(DT, T, ...)                         \
+  switch (DT) {                                             \
+    case kF32: { using T = float; __VA_ARGS__; } break;     \
+    case kF16: { using T = f16; __VA_ARGS__; } break;       \
+    case kBF16: { using T = bf16; __VA_ARGS__; } break;     \
+    default: return -1;                                     \
+  }
+#define APEX_DISPATCH_B(X, NAME, ...)                       \
+  if (X) { constexpr bool NAME = true; __VA_ARGS__; }       \
+  else { constexpr bool NAME = false; __VA_ARGS__; }
+
+#define APEX_HIP_CHECK(expr)                                                   \
   do {                                                                          \
     hipError_t _e = (expr);                                                     \
     if (_e != hipSuccess) return (int)_e;                                       \

@@ -260,14 +260,6 @@ inline int grid_for(int64_t n8) {
 
 }  // namespace
 
-#define FP8_DT(DT, T, ...)                                  \
-  switch (DT) {                                             \
-    case kF32: { using T = float; __VA_ARGS__; } break;     \
-    case kF16: { using T = f16; __VA_ARGS__; } break;       \
-    case kBF16: { using T = bf16; __VA_ARGS__; } break;     \
-    default: return -1;                                     \
-  }
-
 int fp8_quantize(const void* x, uint8_t* y, int64_t n, int dt, int fmt, float* scale, float* scale_inv, float* amax,
                  const float* cur, float smax, hipStream_t s) {
   if (n == 0) return 0;
@@ -275,9 +267,9 @@ int fp8_quantize(const void* x, uint8_t* y, int64_t n, int dt, int fmt, float* s
   const QScale q{scale, scale_inv, amax, cur, smax};
   const int g = grid_for((n + 7) / 8);
   if (fmt == 0) {
-    FP8_DT(dt, T, hipLaunchKernelGGL((quantize_kernel<T, 0>), dim3(g), dim3(256), 0, s, (const T*)x, y, n, q));
+    APEX_DISPATCH_T(dt, T, hipLaunchKernelGGL((quantize_kernel<T, 0>), dim3(g), dim3(256), 0, s, (const T*)x, y, n, q));
   } else {
-    FP8_DT(dt, T, hipLaunchKernelGGL((quantize_kernel<T, 1>), dim3(g), dim3(256), 0, s, (const T*)x, y, n, q));
+    APEX_DISPATCH_T(dt, T, hipLaunchKernelGGL((quantize_kernel<T, 1>), dim3(g), dim3(256), 0, s, (const T*)x, y, n, q));
   }
   return (int)hipGetLastError();
 }
@@ -289,16 +281,16 @@ int fp8_quantize_t(const void* x, uint8_t* y, int R, int C, int dt, int fmt, flo
   const QScale q{scale, scale_inv, amax, cur, smax};
   dim3 grid((C + 63) / 64, (R + 63) / 64);
   if (fmt == 0) {
-    FP8_DT(dt, T, hipLaunchKernelGGL((quantize_t_kernel<T, 0>), grid, dim3(256), 0, s, (const T*)x, y, R, C, q));
+    APEX_DISPATCH_T(dt, T, hipLaunchKernelGGL((quantize_t_kernel<T, 0>), grid, dim3(256), 0, s, (const T*)x, y, R, C, q));
   } else {
-    FP8_DT(dt, T, hipLaunchKernelGGL((quantize_t_kernel<T, 1>), grid, dim3(256), 0, s, (const T*)x, y, R, C, q));
+    APEX_DISPATCH_T(dt, T, hipLaunchKernelGGL((quantize_t_kernel<T, 1>), grid, dim3(256), 0, s, (const T*)x, y, R, C, q));
   }
   return (int)hipGetLastError();
 }
 
 int fp8_amax(const void* x, int64_t n, int dt, float* amax, hipStream_t s) {
   if (n == 0) return 0;
-  FP8_DT(dt, T, hipLaunchKernelGGL((amax_kernel<T>), dim3(grid_for((n + 7) / 8)), dim3(256), 0, s, (const T*)x, n, amax));
+  APEX_DISPATCH_T(dt, T, hipLaunchKernelGGL((amax_kernel<T>), dim3(grid_for((n + 7) / 8)), dim3(256), 0, s, (const T*)x, n, amax));
   return (int)hipGetLastError();
 }
 
@@ -307,12 +299,12 @@ int fp8_quantize_weights(const WqDesc* d, int nd, int64_t ablocks, int64_t qbloc
   if (nd == 0) return 0;
   if (ablocks <= 0 || qblocks <= 0 || ablocks >= (1ll << 31) || qblocks >= (1ll << 31)) return -2;
   hipLaunchKernelGGL(wq_zero_kernel, dim3(1), dim3(256), 0, s, d, nd, amax);
-  FP8_DT(dt, T, hipLaunchKernelGGL((wq_amax_kernel<T>), dim3((int)ablocks), dim3(256), 0, s, d, nd, amax));
+  APEX_DISPATCH_T(dt, T, hipLaunchKernelGGL((wq_amax_kernel<T>), dim3((int)ablocks), dim3(256), 0, s, d, nd, amax));
   if (fmt == 0) {
-    FP8_DT(dt, T, hipLaunchKernelGGL((wq_quant_kernel<T, 0>), dim3((int)qblocks), dim3(256), 0, s, d, nd, scale, scale_inv,
+    APEX_DISPATCH_T(dt, T, hipLaunchKernelGGL((wq_quant_kernel<T, 0>), dim3((int)qblocks), dim3(256), 0, s, d, nd, scale, scale_inv,
                                      amax, smax));
   } else {
-    FP8_DT(dt, T, hipLaunchKernelGGL((wq_quant_kernel<T, 1>), dim3((int)qblocks), dim3(256), 0, s, d, nd, scale, scale_inv,
+    APEX_DISPATCH_T(dt, T, hipLaunchKernelGGL((wq_quant_kernel<T, 1>), dim3((int)qblocks), dim3(256), 0, s, d, nd, scale, scale_inv,
                                      amax, smax));
   }
   return (int)hipGetLastError();

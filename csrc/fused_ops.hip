@@ -12,8 +12,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "fp8_pack.h"
-
-#include <type_traits>
+#include "ln_row.h"
 
 namespace apex {
 
@@ -258,7 +257,7 @@ __global__ void __launch_bounds__(kEwBlock) bdaln_fwd_kernel(const T* __restrict
       }
     }
   }
-  const float rs = rsqrtf(wave_sum(ss) * inv_n + eps);
+  const float rs = ln_rstd(ss, inv_n, eps);
   if (lane == 0) {
     mean[row] = mu;
     rstd[row] = rs;
@@ -430,7 +429,7 @@ __device__ __forceinline__ void bdaln_bwd_body(const T* __restrict__ dy, const T
         float ds[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-          ds[k] = rs * (dv[j][k] * g[j][k] - s1 - xh[j][k] * s2);
+          ds[k] = ln_dx(dv[j][k] * g[j][k], xh[j][k], rs, s1, s2);
           if constexpr (EXTRA) ds[k] += ev[j][k];
         }
         store_f<T, 8>(dres + e, ds);
@@ -580,6 +579,7 @@ __global__ void __launch_bounds__(kEwBlock) bdaln_bwd_wide_kernel(const T* __res
         if constexpr (EXTRA) load_f<T, 8>(dse + e, ev);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
+          // (written out: through ln_dx this kernel alone compiles to different code)
           ds[k] = rs * (dv[k] * g[k] - s1 - (xv[k] - mu) * rs * s2);
           if constexpr (EXTRA) ds[k] += ev[k];
         }
@@ -666,7 +666,7 @@ __global__ void __launch_bounds__(kEwBlock) embed_ln_fwd_kernel(const int* __res
     if (j * 64 + lane < nvec)
 #pragma unroll
       for (int k = 0; k < 8; ++k) ss += (v[j][k] - mu) * (v[j][k] - mu);
-  const float rs = rsqrtf(wave_sum(ss) * inv_n + eps);
+  const float rs = ln_rstd(ss, inv_n, eps);
   if (lane == 0) {
     mean[row] = mu;
     rstd[row] = rs;
@@ -772,7 +772,7 @@ __global__ void __launch_bounds__(kEwBlock) embed_ln_bwd_kernel(const T* __restr
           float d[8];
 #pragma unroll
           for (int k = 0; k < 8; ++k) {
-            d[k] = rs * (dv[j][k] * g[j][k] - s1 - xh[j][k] * s2);
+            d[k] = ln_dx(dv[j][k] * g[j][k], xh[j][k], rs, s1, s2);
             dps[j][k] += d[k];
             if (tt == 0) dt0[j][k] += d[k];
             else dt1[j][k] += d[k];
@@ -838,13 +838,6 @@ __global__ void __launch_bounds__(kEwBlock) embed_segsum_kernel(const T* __restr
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-#define EW_DISPATCH(DT, T, ...)                             \
-  switch (DT) {                                             \
-    case kF32: { using T = float; __VA_ARGS__; } break;     \
-    case kF16: { using T = f16; __VA_ARGS__; } break;       \
-    case kBF16: { using T = bf16; __VA_ARGS__; } break;     \
-    default: return -1;                                     \
-  }
 #define EW_ACT(A, ACT, ...)                                 \
   switch (A) {                                              \
     case 0: { constexpr int ACT = 0; __VA_ARGS__; } break;  \
@@ -879,7 +872,7 @@ int bias_act_fwd(const void* x, const void* b, void* y, int64_t rows, int cols, 
   ColGeom g = col_geom(rows, cols, 512);
   dim3 grid((cols / 8 + kEwBlock - 1) / kEwBlock, (unsigned)((rows + g.rpb - 1) / g.rpb));
   if (!b) bdt = xdt;
-  EW_DISPATCH(xdt, T, EW_DISPATCH(bdt, W, EW_ACT(act, ACT,
+  APEX_DISPATCH_T(xdt, T, APEX_DISPATCH_T(bdt, W, EW_ACT(act, ACT,
       hipLaunchKernelGGL((bias_act_fwd_kernel<T, W, ACT>), grid, dim3(kEwBlock), 0, s, (const T*)x,
                          (const W*)b, (T*)y, g))));
   return (int)hipGetLastError();
@@ -893,7 +886,7 @@ int bias_act_bwd(const void* dy, const void* x, const void* b, void* dx, void* d
   const int parts = (int)((rows + g.rpb - 1) / g.rpb);
   dim3 grid((cols / 8 + kEwBlock - 1) / kEwBlock, parts);
   if (!b) bdt = xdt;
-  EW_DISPATCH(xdt, T, EW_DISPATCH(bdt, W, EW_ACT(act, ACT, {
+  APEX_DISPATCH_T(xdt, T, APEX_DISPATCH_T(bdt, W, EW_ACT(act, ACT, {
     hipLaunchKernelGGL((bias_act_bwd_kernel<T, W, ACT>), grid, dim3(kEwBlock), 0, s, (const T*)dy,
                        (const T*)x, (const W*)b, (T*)dx, db ? ws : nullptr, g);
     if (db)
@@ -910,7 +903,7 @@ int bias_dropout_add_fwd(const void* x, const void* b, const void* res, void* y,
   ColGeom g = col_geom(rows, cols, 512);
   dim3 grid((cols / 8 + kEwBlock - 1) / kEwBlock, (unsigned)((rows + g.rpb - 1) / g.rpb));
   if (!b) bdt = xdt;
-  EW_DISPATCH(xdt, T, EW_DISPATCH(bdt, W, {
+  APEX_DISPATCH_T(xdt, T, APEX_DISPATCH_T(bdt, W, {
     if (thresh)
       hipLaunchKernelGGL((bda_fwd_kernel<T, W, true>), grid, dim3(kEwBlock), 0, s, (const T*)x,
                          (const W*)b, (const T*)res, (T*)y, g, seed, offset, thresh, scale);
@@ -929,7 +922,7 @@ int bias_dropout_add_bwd(const void* dy, void* dx, void* db, float* ws, int64_t 
   ColGeom g = col_geom(rows, cols, 512);
   const int parts = (int)((rows + g.rpb - 1) / g.rpb);
   dim3 grid((cols / 8 + kEwBlock - 1) / kEwBlock, parts);
-  EW_DISPATCH(xdt, T, EW_DISPATCH(bdt, W, {
+  APEX_DISPATCH_T(xdt, T, APEX_DISPATCH_T(bdt, W, {
     if (thresh)
       hipLaunchKernelGGL((bda_bwd_kernel<T, true>), grid, dim3(kEwBlock), 0, s, (const T*)dy, (T*)dx,
                          db ? ws : nullptr, g, seed, offset, thresh, scale);
@@ -1012,87 +1005,29 @@ int splitk_reduce(const float* slabs, void* out, int64_t n, int nsplit, int odt,
   return (int)hipGetLastError();
 }
 
-static inline int bdaln_vpt(int cols) {
-  if (cols % 8) return 0;
-  const int nvec = cols / 8;
-  if (nvec <= 64) return 1;
-  if (nvec <= 128) return 2;
-  if (nvec <= 256) return 4;
-  return 0;
-}
-
+// register-resident rows: up to 4 vectors per lane (the plain LN forward alone goes to 8)
+static inline int bdaln_vpt(int cols) { return ln_vpt(cols, 4); }
 int bdaln_supported(int cols) { return bdaln_vpt(cols) > 0; }
-
 // 2056..4096 columns: forward with 5..8 vectors per lane, backward through bdaln_bwd_wide_kernel
-static inline int bdaln_wide_vpt(int cols) {
-  if (cols % 8) return 0;
-  const int nvec = cols / 8;
-  return (nvec > 256 && nvec <= 512) ? (nvec + 63) / 64 : 0;
-}
-int bdaln_wide_supported(int cols) { return bdaln_wide_vpt(cols) > 0; }
-
-#define EW_VPT_WIDE(V, VPT, ...)                            \
-  switch (V) {                                              \
-    case 5: { constexpr int VPT = 5; __VA_ARGS__; } break;  \
-    case 6: { constexpr int VPT = 6; __VA_ARGS__; } break;  \
-    case 7: { constexpr int VPT = 7; __VA_ARGS__; } break;  \
-    case 8: { constexpr int VPT = 8; __VA_ARGS__; } break;  \
-    default: return -2;                                     \
-  }
-
-#define EW_VPT(V, VPT, ...)                                 \
-  switch (V) {                                              \
-    case 1: { constexpr int VPT = 1; __VA_ARGS__; } break;  \
-    case 2: { constexpr int VPT = 2; __VA_ARGS__; } break;  \
-    case 4: { constexpr int VPT = 4; __VA_ARGS__; } break;  \
-    default: return -2;                                     \
-  }
+int bdaln_wide_supported(int cols) { return ln_wide_vpt(cols) > 0; }
 
 int bdaln_fwd(const void* x, const void* b, const void* res, const void* gamma, const void* beta, void* y,
               void* s_out, float* mean, float* rstd, int64_t rows, int cols, float eps, uint64_t seed,
               uint64_t offset, uint32_t thresh, float scale, int xdt, int wdt, hipStream_t s, Q8Out q8,
               int s_cond) {
   if (rows == 0) return 0;
-  const int vpt = bdaln_vpt(cols);
+  const int vpt = bdaln_vpt(cols) ? bdaln_vpt(cols) : ln_wide_vpt(cols);
   const dim3 grid((unsigned)((rows + 3) / 4));
-  if (!vpt) {
-    const int wv = bdaln_wide_vpt(cols);
-    EW_DISPATCH(xdt, T, EW_DISPATCH(wdt, W, EW_VPT_WIDE(wv, VPT, {
-      if (thresh)
-        hipLaunchKernelGGL((bdaln_fwd_kernel<T, W, VPT, true>), grid, dim3(kEwBlock), 0, s, (const T*)x,
-                           (const W*)b, (const T*)res, (const W*)gamma, (const W*)beta, (T*)y, (T*)s_out,
-                           mean, rstd, rows, cols, eps, seed, offset, thresh, scale, q8, s_cond);
-      else
-        hipLaunchKernelGGL((bdaln_fwd_kernel<T, W, VPT, false>), grid, dim3(kEwBlock), 0, s, (const T*)x,
-                           (const W*)b, (const T*)res, (const W*)gamma, (const W*)beta, (T*)y, (T*)s_out,
-                           mean, rstd, rows, cols, eps, seed, offset, thresh, scale, q8, s_cond);
-    })));
-    return (int)hipGetLastError();
-  }
-  EW_DISPATCH(xdt, T, EW_DISPATCH(wdt, W, EW_VPT(vpt, VPT, {
-    if (thresh)
-      hipLaunchKernelGGL((bdaln_fwd_kernel<T, W, VPT, true>), grid, dim3(kEwBlock), 0, s, (const T*)x,
-                         (const W*)b, (const T*)res, (const W*)gamma, (const W*)beta, (T*)y, (T*)s_out,
-                         mean, rstd, rows, cols, eps, seed, offset, thresh, scale, q8, s_cond);
-    else
-      hipLaunchKernelGGL((bdaln_fwd_kernel<T, W, VPT, false>), grid, dim3(kEwBlock), 0, s, (const T*)x,
-                         (const W*)b, (const T*)res, (const W*)gamma, (const W*)beta, (T*)y, (T*)s_out,
-                         mean, rstd, rows, cols, eps, seed, offset, thresh, scale, q8, s_cond);
-  })));
+  APEX_DISPATCH_T(xdt, T, APEX_DISPATCH_T(wdt, W, LN_DISPATCH_VPT_ANY(vpt, VPT, APEX_DISPATCH_B(thresh, DROP,
+      hipLaunchKernelGGL((bdaln_fwd_kernel<T, W, VPT, DROP>), grid, dim3(kEwBlock), 0, s, (const T*)x,
+                         (const W*)b, (const T*)res, (const W*)gamma, (const W*)beta, (T*)y, (T*)s_out, mean,
+                         rstd, rows, cols, eps, seed, offset, thresh, scale, q8, s_cond)))));
   return (int)hipGetLastError();
-}
-
-// 768 blocks = 3 per CU (the 48 KB combine buffer at cols 1024 allows 3): 12 waves per CU, each
-// with two rows of loads in flight
-constexpr int kBdalnMaxParts = 768;
-static inline int bdaln_rpw(int64_t rows) {
-  const int64_t r = (rows + 4 * kBdalnMaxParts - 1) / (4 * kBdalnMaxParts);
-  return r < 1 ? 1 : (int)r;
 }
 
 int64_t bdaln_ws_floats(int64_t rows, int cols) {
   (void)rows;
-  return (int64_t)kBdalnMaxParts * 3 * (int64_t)cols;
+  return (int64_t)kLnMaxParts * 3 * (int64_t)cols;
 }
 
 int bdaln_bwd(const void* dy, const void* s_in, const void* gamma, const void* beta, const float* mean,
@@ -1101,70 +1036,30 @@ int bdaln_bwd(const void* dy, const void* s_in, const void* gamma, const void* b
               int xdt, int wdt, hipStream_t s, Q8Out q8, const void* s_alt) {
   if (rows == 0) return 0;
   const int vpt = bdaln_vpt(cols);
-  const int rpw = bdaln_rpw(rows);
+  const int rpw = ln_rows_per_wave(rows);
   const int parts = (int)((rows + 4 * rpw - 1) / (4 * rpw));
   if (beta && (!vpt || dse)) return -3;  // FROMY: post-LN (no ds_extra), narrow rows only
   if (q8.y && (!vpt || dse)) return -3;  // fp8 side output: narrow rows, no ds_extra
-  if (!vpt) {
-    const int wv = bdaln_wide_vpt(cols);
-    const size_t wlds = (size_t)4 * cols * sizeof(float);
-    EW_DISPATCH(xdt, T, EW_DISPATCH(wdt, W, EW_VPT_WIDE(wv, VPT, {
-      auto launch = [&](auto drop_tag, auto extra_tag) {
-        hipLaunchKernelGGL((bdaln_bwd_wide_kernel<T, W, VPT, decltype(drop_tag)::value, decltype(extra_tag)::value>),
-                           dim3(parts), dim3(kEwBlock), wlds, s, (const T*)dy, (const T*)s_in, (const W*)gamma,
-                           mean, rstd, (const T*)dse, (T*)dres, (T*)dx, ws, rows, cols, rpw, seed, offset, thresh,
-                           scale);
-      };
-      if (thresh) {
-        if (dse) launch(std::true_type{}, std::true_type{});
-        else launch(std::true_type{}, std::false_type{});
-      } else {
-        if (dse) launch(std::false_type{}, std::true_type{});
-        else launch(std::false_type{}, std::false_type{});
-      }
-      launch_partial_colsum3<W>(ws, parts, 3 * (int64_t)cols, cols, (W*)dgamma, (W*)dbeta, (W*)dbias, s);
-    })));
-    return (int)hipGetLastError();
-  }
-  const size_t lds = (size_t)4 * 3 * cols * sizeof(float);
-  EW_DISPATCH(xdt, T, EW_DISPATCH(wdt, W, EW_VPT(vpt, VPT, {
-    auto launch = [&](auto drop_tag, auto extra_tag) {
-      constexpr bool D = decltype(drop_tag)::value, E = decltype(extra_tag)::value;
-      if (q8.y && !E)
-        hipLaunchKernelGGL((bdaln_bwd_kernel<T, W, VPT, D, false, false, true>), dim3(parts), dim3(kEwBlock), lds, s,
-                           (const T*)dy, (const T*)s_in, (const W*)gamma, (const W*)nullptr, mean, rstd,
-                           (const T*)dse, (T*)dres, (T*)dx, ws, rows, cols, rpw, seed, offset, thresh, scale, q8, (const T*)nullptr);
-      else
-        hipLaunchKernelGGL((bdaln_bwd_kernel<T, W, VPT, D, E>), dim3(parts), dim3(kEwBlock), lds, s, (const T*)dy,
-                           (const T*)s_in, (const W*)gamma, (const W*)nullptr, mean, rstd, (const T*)dse, (T*)dres,
-                           (T*)dx, ws, rows, cols, rpw, seed, offset, thresh, scale, q8, (const T*)nullptr);
-    };
-    if (beta) {
-      auto launch_y = [&](auto drop_tag) {
-        constexpr bool D = decltype(drop_tag)::value;
-        if (q8.y)
-          hipLaunchKernelGGL((bdaln_bwd_kernel<T, W, VPT, D, false, true, true>), dim3(parts), dim3(kEwBlock), lds,
+  APEX_DISPATCH_T(xdt, T, APEX_DISPATCH_T(wdt, W, APEX_DISPATCH_B(thresh, DROP, APEX_DISPATCH_B(dse, EXTRA, {
+    if (vpt) {
+      const size_t lds = (size_t)4 * 3 * cols * sizeof(float);
+      // beta: FROMY (s_in is the LN output, s_alt the conditionally stored LN input)
+      LN_DISPATCH_VPT(vpt, VPT, APEX_DISPATCH_B(beta, FROMY, APEX_DISPATCH_B(q8.y, Q8, {
+        if constexpr (!(EXTRA && (FROMY || Q8)))  // refused above
+          hipLaunchKernelGGL((bdaln_bwd_kernel<T, W, VPT, DROP, EXTRA, FROMY, Q8>), dim3(parts), dim3(kEwBlock), lds,
                              s, (const T*)dy, (const T*)s_in, (const W*)gamma, (const W*)beta, mean, rstd,
-                             (const T*)nullptr, (T*)dres, (T*)dx, ws, rows, cols, rpw, seed, offset, thresh, scale,
-                             q8, (const T*)s_alt);
-        else
-          hipLaunchKernelGGL((bdaln_bwd_kernel<T, W, VPT, D, false, true>), dim3(parts), dim3(kEwBlock), lds, s,
-                             (const T*)dy, (const T*)s_in, (const W*)gamma, (const W*)beta, mean, rstd,
-                             (const T*)nullptr, (T*)dres, (T*)dx, ws, rows, cols, rpw, seed, offset, thresh, scale,
-                             q8, (const T*)s_alt);
-      };
-      if (thresh) launch_y(std::true_type{});
-      else launch_y(std::false_type{});
-    } else if (thresh) {
-      if (dse) launch(std::true_type{}, std::true_type{});
-      else launch(std::true_type{}, std::false_type{});
+                             (const T*)dse, (T*)dres, (T*)dx, ws, rows, cols, rpw, seed, offset, thresh, scale, q8,
+                             (const T*)(FROMY ? s_alt : nullptr));
+      })));
     } else {
-      if (dse) launch(std::false_type{}, std::true_type{});
-      else launch(std::false_type{}, std::false_type{});
+      const size_t lds = (size_t)4 * cols * sizeof(float);
+      LN_DISPATCH_VPT_WIDE(ln_wide_vpt(cols), VPT,
+          hipLaunchKernelGGL((bdaln_bwd_wide_kernel<T, W, VPT, DROP, EXTRA>), dim3(parts), dim3(kEwBlock), lds, s,
+                             (const T*)dy, (const T*)s_in, (const W*)gamma, mean, rstd, (const T*)dse, (T*)dres,
+                             (T*)dx, ws, rows, cols, rpw, seed, offset, thresh, scale));
     }
-    const int64_t ld = 3 * (int64_t)cols;
-    launch_partial_colsum3<W>(ws, parts, ld, cols, (W*)dgamma, (W*)dbeta, (W*)dbias, s);
-  })));
+    launch_partial_colsum3<W>(ws, parts, 3 * (int64_t)cols, cols, (W*)dgamma, (W*)dbeta, (W*)dbias, s);
+  }))));
   return (int)hipGetLastError();
 }
 
@@ -1175,16 +1070,10 @@ int embed_ln_fwd(const int* ids, const int* tids, const void* Ww, const void* Wp
   if (rows == 0) return 0;
   const int vpt = bdaln_vpt(cols);
   const dim3 grid((unsigned)((rows + 3) / 4));
-  EW_DISPATCH(xdt, T, EW_DISPATCH(wdt, W, EW_VPT(vpt, VPT, {
-    if (thresh)
-      hipLaunchKernelGGL((embed_ln_fwd_kernel<T, W, VPT, true>), grid, dim3(kEwBlock), 0, s, ids, tids, (const T*)Ww,
+  APEX_DISPATCH_T(xdt, T, APEX_DISPATCH_T(wdt, W, LN_DISPATCH_VPT(vpt, VPT, APEX_DISPATCH_B(thresh, DROP,
+      hipLaunchKernelGGL((embed_ln_fwd_kernel<T, W, VPT, DROP>), grid, dim3(kEwBlock), 0, s, ids, tids, (const T*)Ww,
                          (const T*)Wp, (const T*)Wt, (const W*)gamma, (const W*)beta, (T*)y, (T*)s_out, mean, rstd,
-                         rows, cols, S, eps, seed, offset, thresh, scale);
-    else
-      hipLaunchKernelGGL((embed_ln_fwd_kernel<T, W, VPT, false>), grid, dim3(kEwBlock), 0, s, ids, tids, (const T*)Ww,
-                         (const T*)Wp, (const T*)Wt, (const W*)gamma, (const W*)beta, (T*)y, (T*)s_out, mean, rstd,
-                         rows, cols, S, eps, seed, offset, thresh, scale);
-  })));
+                         rows, cols, S, eps, seed, offset, thresh, scale)))));
   return (int)hipGetLastError();
 }
 
@@ -1199,15 +1088,11 @@ int embed_ln_bwd(const void* dy, const void* s_in, const void* gamma, const floa
   const int vpt = bdaln_vpt(cols);
   const int nwt = embed_nwt(B);
   const dim3 grid((unsigned)S, (unsigned)(nwt / 4));
-  EW_DISPATCH(xdt, T, EW_DISPATCH(wdt, W, EW_VPT(vpt, VPT, {
-    if (thresh)
-      hipLaunchKernelGGL((embed_ln_bwd_kernel<T, W, VPT, true>), grid, dim3(kEwBlock), 0, s, (const T*)dy,
-                         (const T*)s_in, (const W*)gamma, mean, rstd, tids, (T*)ds_out, part_pos, part_tg, B, cols, S,
-                         nwt, seed, offset, thresh, scale);
-    else
-      hipLaunchKernelGGL((embed_ln_bwd_kernel<T, W, VPT, false>), grid, dim3(kEwBlock), 0, s, (const T*)dy,
-                         (const T*)s_in, (const W*)gamma, mean, rstd, tids, (T*)ds_out, part_pos, part_tg, B, cols, S,
-                         nwt, seed, offset, thresh, scale);
+  APEX_DISPATCH_T(xdt, T, APEX_DISPATCH_T(wdt, W, LN_DISPATCH_VPT(vpt, VPT, {
+    APEX_DISPATCH_B(thresh, DROP,
+        hipLaunchKernelGGL((embed_ln_bwd_kernel<T, W, VPT, DROP>), grid, dim3(kEwBlock), 0, s, (const T*)dy,
+                           (const T*)s_in, (const W*)gamma, mean, rstd, tids, (T*)ds_out, part_pos, part_tg, B, cols,
+                           S, nwt, seed, offset, thresh, scale));
     // position rows: sum over the nwt wave partials; gamma / beta and the two type rows over S * nwt
     launch_partial_colsum3<T>(part_pos, nwt, (int64_t)S * cols, S * cols, (T*)dWp, (T*)nullptr, (T*)nullptr, s);
     launch_partial_colsum3<W>(part_tg, S * nwt, 4 * (int64_t)cols, cols, (W*)dgamma, (W*)dbeta, (W*)nullptr, s);
@@ -1222,7 +1107,7 @@ int embed_segsum(const void* ds, const int* sorted, const int64_t* perm, void* d
   if (R == 0) return 0;
   const int vpt = bdaln_vpt(cols);
   const dim3 grid((unsigned)((R + 3) / 4));
-  EW_DISPATCH(xdt, T, EW_VPT(vpt, VPT,
+  APEX_DISPATCH_T(xdt, T, LN_DISPATCH_VPT(vpt, VPT,
       hipLaunchKernelGGL((embed_segsum_kernel<T, VPT>), grid, dim3(kEwBlock), 0, s, (const T*)ds, sorted, perm, (T*)dW,
                          R, cols)));
   return (int)hipGetLastError();

@@ -10,11 +10,9 @@
 // Slow path (any cols): block-per-row kernels + column-tile dgamma kernel.
 #include "common.h"
 #include "kernels.h"
+#include "ln_row.h"
 
 namespace apex {
-
-constexpr int kLnBlock = 256;
-constexpr int kMaxBwdParts = 768;  // 3 blocks per CU; rows per wave adapts to reach it
 
 template <typename T, typename W, int VPT, bool RMS>
 __global__ void __launch_bounds__(kLnBlock) ln_fwd_fast(const T* __restrict__ x,
@@ -57,7 +55,7 @@ __global__ void __launch_bounds__(kLnBlock) ln_fwd_fast(const T* __restrict__ x,
       }
     }
   }
-  const float rs = rsqrtf(wave_sum(ss) * inv_n + eps);
+  const float rs = ln_rstd(ss, inv_n, eps);
   if (lane == 0) {
     if (mean) mean[row] = mu;
     rstd[row] = rs;
@@ -169,7 +167,7 @@ __global__ void __launch_bounds__(kLnBlock) ln_bwd_fast(const T* __restrict__ dy
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
           const float dyg = dv[j][k] * g[j][k];
-          o[k] = RMS ? rs * (dyg - xh[j][k] * s2) : rs * (dyg - s1 - xh[j][k] * s2);
+          o[k] = ln_dx<RMS>(dyg, xh[j][k], rs, s1, s2);
         }
         store_f<T, 8>(dxr + vi * 8, o);
       }
@@ -270,7 +268,7 @@ __global__ void __launch_bounds__(kLnBlock) ln_bwd_wide(const T* __restrict__ dy
         for (int k = 0; k < 8; ++k) {
           const float xh = (xv[k] - mu) * rs;
           const float dyg = dv[k] * g[k];
-          o[k] = RMS ? rs * (dyg - xh * s2) : rs * (dyg - s1 - xh * s2);
+          o[k] = ln_dx<RMS>(dyg, xh, rs, s1, s2);
         }
         store_f<T, 8>(dxr + vi * 8, o);
       }
@@ -387,51 +385,15 @@ __global__ void __launch_bounds__(kLnBlock) ln_bwd_gb_slow(const T* __restrict__
   out[cols + c] = db;
 }
 
-static inline int ln_vpt(int cols) {
-  if (cols % 8 != 0) return 0;
-  const int nvec = cols / 8;
-  if (nvec <= 64) return 1;
-  if (nvec <= 128) return 2;
-  if (nvec <= 256) return 4;
-  if (nvec <= 512) return 8;
-  return 0;
-}
-
 static inline bool ln_fast_ok(const void* a, const void* b, const void* c, const void* d, int cols) {
   auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  return ln_vpt(cols) > 0 && al(a) && al(b) && al(c) && al(d);
-}
-
-static inline int ln_bwd_rpw(int64_t rows) {
-  const int64_t r = (rows + 4 * kMaxBwdParts - 1) / (4 * kMaxBwdParts);
-  return r < 1 ? 1 : (int)r;
+  return ln_vpt(cols, 8) > 0 && al(a) && al(b) && al(c) && al(d);
 }
 
 int64_t layer_norm_bwd_ws_floats(int64_t rows, int cols) {
   (void)rows;
-  return (int64_t)kMaxBwdParts * 2 * (int64_t)cols;
+  return (int64_t)kLnMaxParts * 2 * (int64_t)cols;
 }
-
-#define LN_DISPATCH_T(DT, T, ...)                           \
-  switch (DT) {                                             \
-    case kF32: { using T = float; __VA_ARGS__; } break;     \
-    case kF16: { using T = f16; __VA_ARGS__; } break;       \
-    case kBF16: { using T = bf16; __VA_ARGS__; } break;     \
-    default: return -1;                                     \
-  }
-
-#define LN_DISPATCH_VPT(V, VPT, ...)                        \
-  switch (V) {                                              \
-    case 1: { constexpr int VPT = 1; __VA_ARGS__; } break;  \
-    case 2: { constexpr int VPT = 2; __VA_ARGS__; } break;  \
-    case 4: { constexpr int VPT = 4; __VA_ARGS__; } break;  \
-    case 8: { constexpr int VPT = 8; __VA_ARGS__; } break;  \
-    default: return -1;                                     \
-  }
-
-#define LN_DISPATCH_RMS(R, RMS, ...)                        \
-  if (R) { constexpr bool RMS = true; __VA_ARGS__; }        \
-  else { constexpr bool RMS = false; __VA_ARGS__; }
 
 int layer_norm_fwd(const void* x, const void* gamma, const void* beta, void* y, float* mean,
                    float* rstd, int64_t rows, int cols, float eps, int xdt, int wdt, int rms,
@@ -439,11 +401,10 @@ int layer_norm_fwd(const void* x, const void* gamma, const void* beta, void* y, 
   if (rows == 0) return 0;
   if (!gamma && !beta) wdt = xdt;
   const bool fast = ln_fast_ok(x, y, gamma, beta, cols);
-  LN_DISPATCH_T(xdt, T, LN_DISPATCH_T(wdt, W, LN_DISPATCH_RMS(rms, RMS, {
+  APEX_DISPATCH_T(xdt, T, APEX_DISPATCH_T(wdt, W, APEX_DISPATCH_B(rms, RMS, {
     if (fast) {
-      const int vpt = ln_vpt(cols);
       const int64_t grid = (rows + 3) / 4;
-      LN_DISPATCH_VPT(vpt, VPT,
+      LN_DISPATCH_VPT8(ln_vpt(cols, 8), VPT,
           hipLaunchKernelGGL((ln_fwd_fast<T, W, VPT, RMS>), dim3((unsigned)grid), dim3(kLnBlock), 0,
                              s, (const T*)x, (const W*)gamma, (const W*)beta, (T*)y, mean, rstd,
                              rows, cols, eps));
@@ -460,38 +421,26 @@ int layer_norm_bwd(const void* dy, const void* x, const void* gamma, const float
                    int cols, int xdt, int wdt, int rms, hipStream_t s) {
   if (rows == 0) return 0;
   if (!gamma) wdt = xdt;
-  const bool fast = ln_fast_ok(x, dy, dx, gamma, cols) && ln_vpt(cols) <= 4;
-  // wide rows: 5..8 16-byte vectors per lane (cols 2056 .. 4096)
-  const int wvpt = (cols % 8 == 0 && cols / 8 > 256 && cols / 8 <= 512) ? (cols / 8 + 63) / 64 : 0;
-  const bool wide = !fast && wvpt > 0 && ln_fast_ok(x, dy, dx, gamma, cols);
+  // register-resident rows up to 4 vectors per lane; wide rows (5..8, cols 2056 .. 4096) are re-read
+  const bool ok = ln_fast_ok(x, dy, dx, gamma, cols);
+  const int vpt = ok ? ln_vpt(cols, 4) : 0, wvpt = ok ? ln_wide_vpt(cols) : 0;
   const bool need_gb = dgamma || dbeta;
-  LN_DISPATCH_T(xdt, T, LN_DISPATCH_T(wdt, W, LN_DISPATCH_RMS(rms, RMS, {
-    int parts;
-    if (fast) {
-      const int vpt = ln_vpt(cols);
-      const int rpw = ln_bwd_rpw(rows);
-      const int64_t rpb = (int64_t)rpw * (kLnBlock / 64);
-      parts = (int)((rows + rpb - 1) / rpb);
+  const int rpw = ln_rows_per_wave(rows);
+  const int64_t rpb = (int64_t)rpw * (kLnBlock / 64);
+  APEX_DISPATCH_T(xdt, T, APEX_DISPATCH_T(wdt, W, APEX_DISPATCH_B(rms, RMS, {
+    int parts = (int)((rows + rpb - 1) / rpb);
+    if (vpt) {
       const size_t lds = (size_t)4 * 2 * cols * sizeof(float);
       LN_DISPATCH_VPT(vpt, VPT,
           hipLaunchKernelGGL((ln_bwd_fast<T, W, VPT, RMS>), dim3(parts), dim3(kLnBlock), lds, s,
                              (const T*)dy, (const T*)x, (const W*)gamma, mean, rstd, (T*)dx, ws,
                              rows, cols, rpw));
-    } else if (wide) {
-      const int rpw = ln_bwd_rpw(rows);
-      const int64_t rpb = (int64_t)rpw * (kLnBlock / 64);
-      parts = (int)((rows + rpb - 1) / rpb);
+    } else if (wvpt) {
       const size_t lds = (size_t)4 * cols * sizeof(float);
-      switch (wvpt) {
-        case 5: hipLaunchKernelGGL((ln_bwd_wide<T, W, 5, RMS>), dim3(parts), dim3(kLnBlock), lds, s, (const T*)dy,
-                                   (const T*)x, (const W*)gamma, mean, rstd, (T*)dx, ws, rows, cols, rpw); break;
-        case 6: hipLaunchKernelGGL((ln_bwd_wide<T, W, 6, RMS>), dim3(parts), dim3(kLnBlock), lds, s, (const T*)dy,
-                                   (const T*)x, (const W*)gamma, mean, rstd, (T*)dx, ws, rows, cols, rpw); break;
-        case 7: hipLaunchKernelGGL((ln_bwd_wide<T, W, 7, RMS>), dim3(parts), dim3(kLnBlock), lds, s, (const T*)dy,
-                                   (const T*)x, (const W*)gamma, mean, rstd, (T*)dx, ws, rows, cols, rpw); break;
-        default: hipLaunchKernelGGL((ln_bwd_wide<T, W, 8, RMS>), dim3(parts), dim3(kLnBlock), lds, s, (const T*)dy,
-                                    (const T*)x, (const W*)gamma, mean, rstd, (T*)dx, ws, rows, cols, rpw); break;
-      }
+      LN_DISPATCH_VPT_WIDE(wvpt, VPT,
+          hipLaunchKernelGGL((ln_bwd_wide<T, W, VPT, RMS>), dim3(parts), dim3(kLnBlock), lds, s,
+                             (const T*)dy, (const T*)x, (const W*)gamma, mean, rstd, (T*)dx, ws,
+                             rows, cols, rpw));
     } else {
       hipLaunchKernelGGL((ln_bwd_dx_slow<T, W, RMS>), dim3((unsigned)rows), dim3(kLnBlock), 0, s,
                          (const T*)dy, (const T*)x, (const W*)gamma, mean, rstd, (T*)dx, cols);

@@ -482,18 +482,11 @@ __global__ void __launch_bounds__(kBlock) larc_kernel(MTMeta m, LarcArgs a, cons
 // ---------------------------------------------------------------------------
 // dtype dispatch
 // ---------------------------------------------------------------------------
-#define APEX_DISPATCH1(DT, T, ...)                          \
-  switch (DT) {                                             \
-    case kF32: { using T = float; __VA_ARGS__; } break;     \
-    case kF16: { using T = f16; __VA_ARGS__; } break;       \
-    case kBF16: { using T = bf16; __VA_ARGS__; } break;     \
-    default: return -1;                                     \
-  }
 
 int mt_scale(const MTMeta& m, int in_dt, int out_dt, const float* sp, float sv, int* overflow,
              hipStream_t s) {
   if (m.nchunks == 0) return 0;
-  APEX_DISPATCH1(in_dt, TI, APEX_DISPATCH1(out_dt, TO,
+  APEX_DISPATCH_T(in_dt, TI, APEX_DISPATCH_T(out_dt, TO,
       hipLaunchKernelGGL((scale_kernel<TI, TO>), dim3(grid_for(m.nchunks)), dim3(kBlock), 0, s, m,
                          sp, sv, overflow)));
   return (int)hipGetLastError();
@@ -502,7 +495,7 @@ int mt_scale(const MTMeta& m, int in_dt, int out_dt, const float* sp, float sv, 
 int mt_axpby(const MTMeta& m, int x_dt, int y_dt, int o_dt, float a, float b, int check,
              int* overflow, hipStream_t s) {
   if (m.nchunks == 0) return 0;
-  APEX_DISPATCH1(x_dt, TX, APEX_DISPATCH1(y_dt, TY, APEX_DISPATCH1(o_dt, TO,
+  APEX_DISPATCH_T(x_dt, TX, APEX_DISPATCH_T(y_dt, TY, APEX_DISPATCH_T(o_dt, TO,
       hipLaunchKernelGGL((axpby_kernel<TX, TY, TO>), dim3(grid_for(m.nchunks)), dim3(kBlock), 0, s,
                          m, a, b, check, overflow))));
   return (int)hipGetLastError();
@@ -511,7 +504,7 @@ int mt_axpby(const MTMeta& m, int x_dt, int y_dt, int o_dt, float a, float b, in
 int mt_l2norm(const MTMeta& m, int list, int dt, float* partial, float* out_tensor,
               float* out_global, const float* sp, float sv, int* overflow, hipStream_t s) {
   if (m.nchunks == 0) return 0;
-  APEX_DISPATCH1(dt, T,
+  APEX_DISPATCH_T(dt, T,
       hipLaunchKernelGGL((sumsq_kernel<T>), dim3(grid_for(m.nchunks)), dim3(kBlock), 0, s, m, list,
                          partial, overflow));
   hipLaunchKernelGGL(norm_finalize_kernel, dim3(m.ntensors + 1), dim3(kBlock), 0, s, m, partial,
@@ -522,7 +515,7 @@ int mt_l2norm(const MTMeta& m, int list, int dt, float* partial, float* out_tens
 int mt_sgd(const MTMeta& m, int g_dt, int p_dt, int c_dt, const SgdArgs& a, hipStream_t s) {
   if (m.nchunks == 0) return 0;
   if (m.nlists <= 3) c_dt = p_dt;
-  APEX_DISPATCH1(g_dt, G, APEX_DISPATCH1(p_dt, P, APEX_DISPATCH1(c_dt, C,
+  APEX_DISPATCH_T(g_dt, G, APEX_DISPATCH_T(p_dt, P, APEX_DISPATCH_T(c_dt, C,
       hipLaunchKernelGGL((sgd_kernel<G, P, C>), dim3(grid_for(m.nchunks)), dim3(kBlock), 0, s, m,
                          a))));
   if (a.first_run_dev)
@@ -536,7 +529,7 @@ int mt_adam(const MTMeta& m, int g_dt, int p_dt, int c_dt, const AdamArgs& a, hi
   if (a.step)
     hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(1), 0, s, a.step, a.noop, a.beta1, a.beta2,
                        a.bias_correction, a.scal);
-  APEX_DISPATCH1(g_dt, G, APEX_DISPATCH1(p_dt, P, APEX_DISPATCH1(c_dt, C,
+  APEX_DISPATCH_T(g_dt, G, APEX_DISPATCH_T(p_dt, P, APEX_DISPATCH_T(c_dt, C,
       hipLaunchKernelGGL((adam_kernel<G, P, C>), dim3(grid_for(m.nchunks)), dim3(kBlock), 0, s, m,
                          a))));
   return (int)hipGetLastError();
@@ -556,19 +549,19 @@ int mt_lamb(const MTMeta& m, int g_dt, int p_dt, int c_dt, const LambArgs& a, fl
   float* unorm = pnorm + T;
   const int grid = grid_for(C);
   if (!a.gnorm_in) {
-    APEX_DISPATCH1(g_dt, G,
+    APEX_DISPATCH_T(g_dt, G,
         hipLaunchKernelGGL((sumsq_kernel<G>), dim3(grid), dim3(kBlock), 0, s, m, 0, gpart,
                            a.overflow_out));
   }
   hipLaunchKernelGGL(lamb_prep_kernel, dim3(1), dim3(kBlock), 0, s, gpart, C, a, scal, step);
-  APEX_DISPATCH1(g_dt, G, APEX_DISPATCH1(p_dt, P,
+  APEX_DISPATCH_T(g_dt, G, APEX_DISPATCH_T(p_dt, P,
       hipLaunchKernelGGL((lamb_stage1_kernel<G, P>), dim3(grid), dim3(kBlock), 0, s, m, a, scal,
                          ppart, upart)));
   hipLaunchKernelGGL(norm_finalize_kernel, dim3(T), dim3(kBlock), 0, s, m, ppart, pnorm,
                      (float*)nullptr, (const float*)nullptr, 1.f);
   hipLaunchKernelGGL(norm_finalize_kernel, dim3(T), dim3(kBlock), 0, s, m, upart, unorm,
                      (float*)nullptr, (const float*)nullptr, 1.f);
-  APEX_DISPATCH1(p_dt, P, APEX_DISPATCH1(c_dt, C,
+  APEX_DISPATCH_T(p_dt, P, APEX_DISPATCH_T(c_dt, C,
       hipLaunchKernelGGL((lamb_stage2_kernel<P, C>), dim3(grid), dim3(kBlock), 0, s, m, a, scal, pnorm,
                          unorm)));
   return (int)hipGetLastError();
@@ -582,17 +575,17 @@ int mt_larc(const MTMeta& m, int g_dt, int p_dt, const LarcArgs& a, float* ws, h
   float* pnorm = ws + C;
   float* gnorm = pnorm + T;
   const int grid = grid_for(C);
-  APEX_DISPATCH1(p_dt, P,
+  APEX_DISPATCH_T(p_dt, P,
       hipLaunchKernelGGL((sumsq_kernel<P>), dim3(grid), dim3(kBlock), 0, s, m, 1, part,
                          (int*)nullptr));
   hipLaunchKernelGGL(norm_finalize_kernel, dim3(T), dim3(kBlock), 0, s, m, part, pnorm,
                      (float*)nullptr, (const float*)nullptr, 1.f);
-  APEX_DISPATCH1(g_dt, G,
+  APEX_DISPATCH_T(g_dt, G,
       hipLaunchKernelGGL((sumsq_kernel<G>), dim3(grid), dim3(kBlock), 0, s, m, 0, part,
                          (int*)nullptr));
   hipLaunchKernelGGL(norm_finalize_kernel, dim3(T), dim3(kBlock), 0, s, m, part, gnorm,
                      (float*)nullptr, (const float*)nullptr, 1.f);
-  APEX_DISPATCH1(g_dt, G, APEX_DISPATCH1(p_dt, P,
+  APEX_DISPATCH_T(g_dt, G, APEX_DISPATCH_T(p_dt, P,
       hipLaunchKernelGGL((larc_kernel<G, P>), dim3(grid), dim3(kBlock), 0, s, m, a, pnorm,
                          gnorm)));
   return (int)hipGetLastError();

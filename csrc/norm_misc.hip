@@ -16,13 +16,6 @@
 
 namespace apex {
 
-#define NM_DISPATCH(DT, T, ...)                             \
-  switch (DT) {                                             \
-    case kF32: { using T = float; __VA_ARGS__; } break;     \
-    case kF16: { using T = f16; __VA_ARGS__; } break;       \
-    case kBF16: { using T = bf16; __VA_ARGS__; } break;     \
-    default: return -1;                                     \
-  }
 
 // ============================ weight norm ===================================
 template <typename T, typename G>
@@ -96,7 +89,7 @@ __global__ void __launch_bounds__(256) wn_col_bwd(const T* __restrict__ dw, cons
 int weight_norm_fwd(const void* v, const void* g, void* w, float* norms, int64_t R, int64_t C, int row_mode,
                     int vdt, int gdt, hipStream_t s) {
   if (R == 0 || C == 0) return 0;
-  NM_DISPATCH(vdt, T, NM_DISPATCH(gdt, G, {
+  APEX_DISPATCH_T(vdt, T, APEX_DISPATCH_T(gdt, G, {
     if (row_mode)
       hipLaunchKernelGGL((wn_row_fwd<T, G>), dim3((unsigned)R), dim3(256), 0, s, (const T*)v, (const G*)g,
                          (T*)w, norms, C);
@@ -110,7 +103,7 @@ int weight_norm_fwd(const void* v, const void* g, void* w, float* norms, int64_t
 int weight_norm_bwd(const void* dw, const void* v, const void* g, const float* norms, void* dv, void* dg,
                     int64_t R, int64_t C, int row_mode, int vdt, int gdt, hipStream_t s) {
   if (R == 0 || C == 0) return 0;
-  NM_DISPATCH(vdt, T, NM_DISPATCH(gdt, G, {
+  APEX_DISPATCH_T(vdt, T, APEX_DISPATCH_T(gdt, G, {
     if (row_mode)
       hipLaunchKernelGGL((wn_row_bwd<T, G>), dim3((unsigned)R), dim3(256), 0, s, (const T*)dw, (const T*)v,
                          (const G*)g, norms, (T*)dv, (G*)dg, C);
@@ -233,7 +226,7 @@ int lstm_cell_fwd(const void* ig, const void* hg, const void* bih, const void* b
                   void* cy, float* ws, int64_t B, int64_t H, int dt, hipStream_t s) {
   const int64_t n = B * H;
   if (n == 0) return 0;
-  NM_DISPATCH(dt, T,
+  APEX_DISPATCH_T(dt, T,
       hipLaunchKernelGGL((lstm_fwd_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
                          (const T*)ig, (const T*)hg, (const T*)bih, (const T*)bhh, (const T*)cx, (T*)hy,
                          (T*)cy, ws, B, H));
@@ -244,7 +237,7 @@ int lstm_cell_bwd(const void* dhy, const void* dcy, const void* cx, const float*
                   int64_t B, int64_t H, int dt, hipStream_t s) {
   const int64_t n = B * H;
   if (n == 0) return 0;
-  NM_DISPATCH(dt, T,
+  APEX_DISPATCH_T(dt, T,
       hipLaunchKernelGGL((lstm_bwd_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
                          (const T*)dhy, (const T*)dcy, (const T*)cx, ws, (T*)dgates, (T*)dcx, B, H));
   return (int)hipGetLastError();
@@ -254,7 +247,7 @@ int gru_cell_fwd(const void* ig, const void* hg, const void* bih, const void* bh
                  float* ws, int64_t B, int64_t H, int dt, hipStream_t s) {
   const int64_t n = B * H;
   if (n == 0) return 0;
-  NM_DISPATCH(dt, T,
+  APEX_DISPATCH_T(dt, T,
       hipLaunchKernelGGL((gru_fwd_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
                          (const T*)ig, (const T*)hg, (const T*)bih, (const T*)bhh, (const T*)hx, (T*)hy, ws,
                          B, H));
@@ -265,7 +258,7 @@ int gru_cell_bwd(const void* dhy, const void* hx, const float* ws, void* dig, vo
                  int64_t H, int dt, hipStream_t s) {
   const int64_t n = B * H;
   if (n == 0) return 0;
-  NM_DISPATCH(dt, T,
+  APEX_DISPATCH_T(dt, T,
       hipLaunchKernelGGL((gru_bwd_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
                          (const T*)dhy, (const T*)hx, ws, (T*)dig, (T*)dhg, (T*)dhx, B, H));
   return (int)hipGetLastError();
@@ -938,16 +931,16 @@ int bn_stats(const void* x, float* part, int64_t N, int64_t C, int64_t S, int nh
     if (nhwc) {
       int cvb, rpb, gx;
       bn_nhwc_geom(C, V, cvb, rpb, gx);
-      NM_DISPATCH(dt, T,
+      APEX_DISPATCH_T(dt, T,
           hipLaunchKernelGGL((bn_stats_nhwc_vec<T>), dim3(gx, sp), dim3(256), 0, s, (const T*)x, part, N * S,
                              (int)C, cvb, rpb));
     } else {
-      NM_DISPATCH(dt, T,
+      APEX_DISPATCH_T(dt, T,
           hipLaunchKernelGGL((bn_stats_nchw_vec<T>), dim3((unsigned)C, sp), dim3(256), 0, s, (const T*)x, part,
                              (int)N, (int)C, (int)S));
     }
   } else {
-    NM_DISPATCH(dt, T,
+    APEX_DISPATCH_T(dt, T,
         hipLaunchKernelGGL((bn_stats_kernel<T>), dim3((unsigned)C, sp), dim3(256), 0, s, (const T*)x, part, N, C,
                            S, nhwc));
   }
@@ -977,18 +970,18 @@ int bn_elemt(const void* x, const float* mean, const float* invstd, const void* 
   const int V = bn_vec(dt);
   if (coef && bn_vec_ok(x, N, C, S, nhwc, V) && ((uintptr_t)y & 15) == 0 && ((uintptr_t)coef & 15) == 0 &&
       ((uintptr_t)z & 15) == 0) {
-    NM_DISPATCH(wdt, W,
+    APEX_DISPATCH_T(wdt, W,
         hipLaunchKernelGGL((bn_coef_fwd_kernel<W>), dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, mean, invstd,
                            (const W*)w, (const W*)b, coef, (int)C));
     const int64_t nvec = total / V;
     const int64_t grid = min((nvec + 255) / 256, (int64_t)4096);
-    NM_DISPATCH(dt, T,
+    APEX_DISPATCH_T(dt, T,
         hipLaunchKernelGGL((bn_elemt_vec<T>), dim3((unsigned)grid), dim3(256), 0, s, (const T*)x, coef, (const T*)z,
                            (T*)y, (int)nvec, (int)C, (int)S, nhwc, relu));
     return (int)hipGetLastError();
   }
   const int64_t grid = min((total + 255) / 256, (int64_t)8192);
-  NM_DISPATCH(dt, T, NM_DISPATCH(wdt, W,
+  APEX_DISPATCH_T(dt, T, APEX_DISPATCH_T(wdt, W,
       hipLaunchKernelGGL((bn_elemt_kernel<T, W>), dim3((unsigned)grid), dim3(256), 0, s, (const T*)x, mean,
                          invstd, (const W*)w, (const W*)b, (const T*)z, (T*)y, N, C, S, nhwc, relu)));
   return (int)hipGetLastError();
@@ -1003,16 +996,16 @@ int bn_bwd_reduce(const void* dy, const void* x, const void* ym, const float* me
     if (nhwc) {
       int cvb, rpb, gx;
       bn_nhwc_geom(C, V, cvb, rpb, gx);
-      NM_DISPATCH(dt, T,
+      APEX_DISPATCH_T(dt, T,
           hipLaunchKernelGGL((bn_bwd_reduce_nhwc_vec<T>), dim3(gx, sp), dim3(256), 0, s, (const T*)dy,
                              (const T*)x, (const T*)ym, mean, part, N * S, (int)C, cvb, rpb));
     } else {
-      NM_DISPATCH(dt, T,
+      APEX_DISPATCH_T(dt, T,
           hipLaunchKernelGGL((bn_bwd_reduce_nchw_vec<T>), dim3((unsigned)C, sp), dim3(256), 0, s, (const T*)dy,
                              (const T*)x, (const T*)ym, mean, part, (int)N, (int)C, (int)S));
     }
   } else {
-    NM_DISPATCH(dt, T,
+    APEX_DISPATCH_T(dt, T,
         hipLaunchKernelGGL((bn_bwd_reduce_kernel<T>), dim3((unsigned)C, sp), dim3(256), 0, s, (const T*)dy,
                            (const T*)x, (const T*)ym, mean, part, N, C, S, nhwc));
   }
@@ -1033,18 +1026,18 @@ int bn_bwd_elemt(const void* dy, const void* x, const float* mean, const float* 
   const int V = bn_vec(dt);
   if (coef && bn_vec_ok(x, N, C, S, nhwc, V) && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)dx & 15) == 0 &&
       ((uintptr_t)coef & 15) == 0 && ((uintptr_t)ym & 15) == 0 && ((uintptr_t)dz & 15) == 0) {
-    NM_DISPATCH(wdt, W,
+    APEX_DISPATCH_T(wdt, W,
         hipLaunchKernelGGL((bn_coef_bwd_kernel<W>), dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, mean, invstd,
                            (const W*)w, sum_dy, sum_dy_xmu, count, coef, (int)C));
     const int64_t nvec = total / V;
     const int64_t grid = min((nvec + 255) / 256, (int64_t)4096);
-    NM_DISPATCH(dt, T,
+    APEX_DISPATCH_T(dt, T,
         hipLaunchKernelGGL((bn_bwd_elemt_vec<T>), dim3((unsigned)grid), dim3(256), 0, s, (const T*)dy, (const T*)x,
                            coef, (const T*)ym, (T*)dz, (T*)dx, (int)nvec, (int)C, (int)S, nhwc));
     return (int)hipGetLastError();
   }
   const int64_t grid = min((total + 255) / 256, (int64_t)8192);
-  NM_DISPATCH(dt, T, NM_DISPATCH(wdt, W,
+  APEX_DISPATCH_T(dt, T, APEX_DISPATCH_T(wdt, W,
       hipLaunchKernelGGL((bn_bwd_elemt_kernel<T, W>), dim3((unsigned)grid), dim3(256), 0, s, (const T*)dy,
                          (const T*)x, mean, invstd, (const W*)w, sum_dy, sum_dy_xmu, count, (const T*)ym,
                          (T*)dz, (T*)dx, N, C, S, nhwc)));

@@ -102,13 +102,6 @@ __global__ void __launch_bounds__(256) smx_bwd_kernel(const T* __restrict__ dy, 
   }
 }
 
-#define SMX_DISPATCH(DT, T, ...)                            \
-  switch (DT) {                                             \
-    case kF32: { using T = float; __VA_ARGS__; } break;     \
-    case kF16: { using T = f16; __VA_ARGS__; } break;       \
-    case kBF16: { using T = bf16; __VA_ARGS__; } break;     \
-    default: return -1;                                     \
-  }
 #define SMX_KPL(C, KPL, ...)                                \
   if ((C) <= 512) { constexpr int KPL = 1; __VA_ARGS__; }   \
   else if ((C) <= 1024) { constexpr int KPL = 2; __VA_ARGS__; } \
@@ -123,7 +116,7 @@ int scaled_masked_softmax_fwd(const void* x, const uint8_t* mask, void* y, int64
   if (rows == 0) return 0;
   if (!scaled_softmax_supported(cols)) return -2;
   const dim3 grid((unsigned)((rows + 3) / 4));
-  SMX_DISPATCH(dt, T, SMX_KPL(cols, KPL, {
+  APEX_DISPATCH_T(dt, T, SMX_KPL(cols, KPL, {
     if (mode == 0)
       hipLaunchKernelGGL((smx_fwd_kernel<T, KPL, 0>), grid, dim3(256), 0, s, (const T*)x, mask, (T*)y, rows, cols,
                          sq, heads, mask_heads, scale);
@@ -142,7 +135,7 @@ int scaled_masked_softmax_bwd(const void* dy, const void* y, void* dx, int64_t r
   if (rows == 0) return 0;
   if (!scaled_softmax_supported(cols)) return -2;
   const dim3 grid((unsigned)((rows + 3) / 4));
-  SMX_DISPATCH(dt, T, SMX_KPL(cols, KPL,
+  APEX_DISPATCH_T(dt, T, SMX_KPL(cols, KPL,
       hipLaunchKernelGGL((smx_bwd_kernel<T, KPL>), grid, dim3(256), 0, s, (const T*)dy, (const T*)y, (T*)dx, rows,
                          cols, scale)));
   return (int)hipGetLastError();

@@ -124,19 +124,12 @@ __global__ void __launch_bounds__(kXeBlock) xent_bwd_kernel(const G* __restrict_
   }
 }
 
-#define XE_DISPATCH(DT, T, ...)                             \
-  switch (DT) {                                             \
-    case kF32: { using T = float; __VA_ARGS__; } break;     \
-    case kF16: { using T = f16; __VA_ARGS__; } break;       \
-    case kBF16: { using T = bf16; __VA_ARGS__; } break;     \
-    default: return -1;                                     \
-  }
 
 int xentropy_fwd(const void* logits, const int64_t* labels, float* losses, float* lse, int64_t rows,
                  int V, float smoothing, int64_t ignore_index, int dt, hipStream_t s) {
   if (rows == 0) return 0;
   const int vec = (V % 8 == 0) && (((uintptr_t)logits & 15) == 0);
-  XE_DISPATCH(dt, T,
+  APEX_DISPATCH_T(dt, T,
       hipLaunchKernelGGL((xent_fwd_kernel<T>), dim3((unsigned)rows), dim3(kXeBlock), 0, s,
                          (const T*)logits, labels, losses, lse, V, smoothing, ignore_index, vec));
   return (int)hipGetLastError();
@@ -147,7 +140,7 @@ int xentropy_bwd(const void* dloss, int64_t dloss_stride, int dloss_dt, const vo
                  float smoothing, int64_t ignore_index, int dt, hipStream_t s) {
   if (rows == 0) return 0;
   const int vec = (V % 8 == 0) && (((uintptr_t)logits & 15) == 0) && (((uintptr_t)dlogits & 15) == 0);
-  XE_DISPATCH(dt, T, XE_DISPATCH(dloss_dt, G,
+  APEX_DISPATCH_T(dt, T, APEX_DISPATCH_T(dloss_dt, G,
       hipLaunchKernelGGL((xent_bwd_kernel<T, G>), dim3((unsigned)rows), dim3(kXeBlock), 0, s,
                          (const G*)dloss, dloss_stride, (const T*)logits, lse, labels, (T*)dlogits,
                          V, smoothing, ignore_index, vec)));

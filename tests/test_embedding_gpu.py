@@ -28,7 +28,10 @@ def _ref(ids, tids, Ww, Wp, Wt, gamma, beta, eps, mask=None, p=0.0):
 
 
 @pytest.mark.parametrize("B,S,H,V,dup", [(4, 128, 1024, 30528, False), (8, 64, 768, 1000, True),
-                                         (3, 40, 256, 50, True), (2, 16, 512, 7, True)])
+                                         (3, 40, 256, 50, True), (2, 16, 512, 7, True),
+                                         # B > 16: the 16 backward waves of a position walk several batch
+                                         # rows (18: waves 0-1 two, the rest one; 35: three and two)
+                                         (18, 8, 768, 50, True), (35, 4, 256, 7, True)])
 @pytest.mark.parametrize("types", [True, False])
 def test_embeddings_match_fp32_reference(B, S, H, V, dup, types):
     from apex.ops.fused import bert_embeddings

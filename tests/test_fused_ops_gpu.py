@@ -265,3 +265,66 @@ def test_bdaln_conditional_s_zero_gamma(zero, cols, p):
         else:
             err = (a.float() - r.float()).abs().max().item() / (r.float().abs().max().item() + 1e-6)
             assert err < 2e-2, (name, err)  # rebuilt from y (the sentinel s_alt is never read)
+
+
+@pytest.mark.parametrize("cols,p,mode", [(768, 0.0, "plain"), (768, 0.1, "plain"), (1024, 0.0, "plain"),
+                                         (1024, 0.1, "plain"), (2560, 0.0, "extra"), (768, 0.0, "fromy")])
+def test_bdaln_bwd_ragged_multirow(cols, p, mode):
+    """rows = 3077: every wave of the backward walks two rows (rows > 3072) and the last block is ragged
+    (5 rows over 4 waves), so the next-row prefetch, its `row < rows` guard and the early `break` all
+    run. cols 768: two vectors per lane with half of the second idle; 2560: the wide kernel, with the
+    second gradient of the residual stream (ds_extra); fromy: backward from the LN output.
+    Gradients against fp32 autograd (dropout mask recovered from a forward of ones), and for p = 0
+    exact row independence: the backward of the first 3072 rows alone (one row per wave) gives bit for
+    bit the first 3072 rows of dres / dx — a prefetch that hands a wave the wrong row cannot."""
+    C = _C()
+    dt = torch.bfloat16
+    torch.manual_seed(cols)
+    rows, cut = 3077, 3072
+    t = torch.randn(rows, cols, device=DEV).to(dt)
+    b = (0.1 * torch.randn(cols, device=DEV)).to(dt)
+    res = torch.randn(rows, cols, device=DEV).to(dt)
+    g = (1 + 0.1 * torch.randn(cols, device=DEV)).to(dt)
+    be = (0.1 * torch.randn(cols, device=DEV)).to(dt)
+    dy = torch.randn(rows, cols, device=DEV).to(dt)
+    ds = torch.randn(rows, cols, device=DEV).to(dt) if mode == "extra" else None
+    y, s, mean, rstd = C.bdaln_fwd(t, b, res, g, be, 1e-5, p, 11, 3)
+    keep = torch.ones(rows, cols, device=DEV)
+    if p:  # same seed and offset, res = 0, x + b = 1 -> the kept entries are exactly 1 / (1 - p)
+        one = torch.ones(rows, cols, device=DEV, dtype=dt)
+        keep = C.bdaln_fwd(one, torch.zeros_like(b), torch.zeros_like(one), g, be, 1e-5, p, 11, 3)[1].float()
+        assert 0.05 < float((keep == 0).float().mean()) < 0.15
+
+    def bwd(n):
+        kw = {} if ds is None else {"ds_extra": ds[:n]}
+        if mode == "fromy":
+            y2, s2, mean2, rstd2 = C.bdaln_fwd(t[:n], b, res[:n], g, be, 1e-5, p, 11, 3, store_s=False)
+            assert s2.numel() == 0 and torch.equal(y2, y[:n])
+            return C.bdaln_bwd(dy[:n], y2, g, mean2, rstd2, p, 11, 3, True, beta=be)
+        return C.bdaln_bwd(dy[:n], s[:n], g, mean[:n], rstd[:n], p, 11, 3, True, **kw)
+
+    got = bwd(rows)
+    names = ("dres", "dx", "dgamma", "dbeta", "dbias")
+    tr, br, rr, gr, ber = [x.float().requires_grad_(True) for x in (t, b, res, g, be)]
+    sr = rr + (tr + br) * keep
+    yr = F.layer_norm(sr, (cols,), gr, ber, 1e-5)
+    torch.autograd.backward([yr] + ([sr] if ds is not None else []), [dy.float()] + ([ds.float()] if ds is not None else []))
+    ref = (rr.grad, tr.grad, gr.grad, ber.grad, br.grad)
+    if mode == "fromy":  # the tolerances of test_bdaln_bwd_from_output_matches_stored_input
+        stored = C.bdaln_bwd(dy, s, g, mean, rstd, p, 11, 3, True)
+        for a, r, name in zip(got, stored, names):
+            err = (a.float() - r.float()).abs().max().item() / (r.float().abs().max().item() + 1e-6)
+            print(name, "vs stored", err)
+            assert err < 2e-2, (name, err)
+        for i in (0, 2, 3):
+            err = (got[i].float() - ref[i]).abs().max().item() / (ref[i].abs().max().item() + 1e-6)
+            print(names[i], "vs fp32", err)
+            assert err < 4 * 3e-2, (names[i], err)
+    else:  # the tolerance of test_bias_dropout_add_ln_vs_fp32
+        for a, r, name in zip(got, ref, names):
+            err = float((a.float() - r).norm() / r.norm())
+            print(name, err)
+            assert err < 1e-2, (name, err)
+    if p == 0.0:
+        part = bwd(cut)
+        assert torch.equal(part[0], got[0][:cut]) and torch.equal(part[1], got[1][:cut])

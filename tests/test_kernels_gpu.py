@@ -178,6 +178,32 @@ def test_layer_norm_fwd_bwd(dt, cols, rows, rms):
         torch.testing.assert_close(mod.bias.grad.float(), b.grad, rtol=tol * 4, atol=tol * 40)
 
 
+@pytest.mark.parametrize("cols", [768, 2560])
+@pytest.mark.parametrize("rms", [False, True])
+def test_layer_norm_bwd_row_independence(cols, rms):
+    """rows = 3077: two rows per wave in the backward (rows > 3072), ragged last block. dx of a row
+    depends on that row only, so the backward of the first 3072 rows alone (one row per wave) must give
+    bit for bit the first 3072 rows of dx (768: ln_bwd_fast and its next-row prefetch, 2560: ln_bwd_wide)."""
+    from apex.normalization import FusedLayerNorm, FusedRMSNorm
+
+    torch.manual_seed(cols)
+    rows, cut = 3077, 3072
+    dt = torch.bfloat16
+    mod = (FusedRMSNorm if rms else FusedLayerNorm)(cols).to(DEV).to(dt)
+    with torch.no_grad():
+        mod.weight.normal_()
+    x = torch.randn(rows, cols, device=DEV).to(dt)
+    dy = torch.randn(rows, cols, device=DEV).to(dt)
+    dx = []
+    for n in (rows, cut):
+        xn = x[:n].clone().requires_grad_(True)
+        mod(xn).backward(dy[:n].clone())
+        dx.append(xn.grad)
+    assert torch.isfinite(dx[0].float()).all() and float(dx[0].float().abs().max()) > 0
+    assert torch.equal(dx[1], dx[0][:cut])
+
+
+
 @pytest.mark.parametrize("dt", DTYPES)
 @pytest.mark.parametrize("V", [30528, 1000, 50257])
 @pytest.mark.parametrize("smoothing", [0.0, 0.1])

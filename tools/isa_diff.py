@@ -6,7 +6,8 @@ Splits both files by kernel symbol (every .amdhsa_kernel name). A kernel's text 
 instructions (from its label to .Lfunc_end) plus its .amdhsa_kernel descriptor (registers,
 scratch, LDS, kernarg size). Normalised is only what necessarily moves when code is
 rearranged in the source: the function index inside local labels (.LBB<n>_, .Lfunc_end<n>, and
-the same BB<n>_ label named in a block comment).
+the same BB<n>_ label named in a block comment), and the padding between a label and its comment, whose
+column depends on how many digits <n> has.
 Lines outside kernels (.file, .ident, the __hip_cuid_* symbol, metadata) are not compared. A device
 function that is not inlined would be a symbol of its own outside every kernel: such symbols
 (.type <sym>,@function without a descriptor) are counted and, if there are any, fail the run.
@@ -39,7 +40,8 @@ def kernels(path):
             cur = None
             continue
         # .LBB<n>_<k> (and BB<n>_<k> in the block comments), .Lfunc_end<n>: <n> is the function's index
-        out[cur].append(re.sub(r"(\.LBB|\bBB|\.Lfunc_end)\d+", r"\1", l))
+        # (and the padding in front of a label's comment, whose column moves with the digits of <n>)
+        out[cur].append(re.sub(r"^(\.LBB_\d+:)\s*;", r"\1 ;", re.sub(r"(\.LBB|\bBB|\.Lfunc_end)\d+", r"\1", l)))
         if mode == "desc" and s == ".end_amdhsa_kernel":
             cur = None
     return out, others
