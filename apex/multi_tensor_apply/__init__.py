@@ -2,8 +2,10 @@
 
 ``MTPlan`` (C++ in csrc/bindings.cpp) is a device-resident chunk table for N
 parallel tensor lists; every fused op is ONE launch over every chunk of every
-tensor. Plans are cached by tensor identity and re-validated by raw pointer in
-C++, so a steady-state training step performs no metadata upload.
+tensor. Plans are cached by tensor identity and re-validated in C++ by raw pointer,
+numel and dtype of every tensor (a ``resize_``, a reinterpreting ``view(dtype)`` or a
+recycled ``id()`` on a recycled allocation keeps the pointer), so a steady-state
+training step performs no metadata upload.
 
 Public API mirrors later apex releases:
     multi_tensor_applier(op, noop_flag_buffer, tensor_lists, *args)

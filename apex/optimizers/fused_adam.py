@@ -15,6 +15,7 @@ master_weights=False, max_grad_norm=0.)``.
   instead of ``p.grad``, 16-bit ``output_params`` written with the updated fp32 parameters, grads
   divided by ``scale``, and with ``max_grad_norm > 0`` clipped by ``grad_norms`` (the global norm
   of the scaled grads): combined scale = scale * max(1, (norm / scale + 1e-6) / max_grad_norm).
+  With amp's device gradient scale attached as well, the kernel applies both factors.
 """
 
 from __future__ import annotations
@@ -120,5 +121,5 @@ class FusedAdam(FusedOptimizerBase):
                 mt_ops.multi_tensor_adam(0, self._amp_noop, lists, group["lr"], b1, b2,
                                          group["eps"], group["step"], self.adam_w_mode,
                                          group["bias_correction"], group["weight_decay"],
-                                         scale_t if scale_t is not None else gscale)
+                                         scale_t * gscale if scale_t is not None else gscale)
         return loss

@@ -44,6 +44,7 @@ struct MTPlan {
   int nlists = 0, ntensors = 0, nchunks = 0, chunk_size = 0, aligned = 1;
   std::vector<int> dtypes;
   std::vector<int64_t> host_ptrs;
+  std::vector<int64_t> host_numel;  // [ntensors]
 
   MTPlan(const std::vector<std::vector<Tensor>>& lists, int64_t chunk) {
     TORCH_CHECK(!lists.empty() && lists.size() <= (size_t)apex::kMaxLists, "bad list count");
@@ -78,6 +79,7 @@ struct MTPlan {
     }
     chunk_off[ntensors] = (int64_t)chunks.size();
     nchunks = (int)chunks.size();
+    host_numel = numel;
     const int64_t words = apex::mt_meta_words(nlists, ntensors, nchunks);
     Tensor host = at::empty({words}, at::TensorOptions().dtype(at::kLong).pinned_memory(true));
     int64_t* h = host.data_ptr<int64_t>();
@@ -100,13 +102,21 @@ struct MTPlan {
     meta = host.to(dev, /*non_blocking=*/true);
   }
 
+  // The chunk table and the dtype dispatch were built from pointer, numel and dtype, so all three
+  // must still hold: resize_, a reinterpreting view(dtype) or a recycled allocation keep the
+  // pointer and change the rest.
   bool matches(const std::vector<std::vector<Tensor>>& lists) const {
     if ((int)lists.size() != nlists) return false;
     for (int l = 0; l < nlists; ++l) {
       if ((int)lists[l].size() != ntensors) return false;
-      for (int t = 0; t < ntensors; ++t)
-        if ((int64_t)(uintptr_t)lists[l][t].data_ptr() != host_ptrs[(size_t)l * ntensors + t])
-          return false;
+      for (int t = 0; t < ntensors; ++t) {
+        const Tensor& x = lists[l][t];
+        if ((int64_t)(uintptr_t)x.data_ptr() != host_ptrs[(size_t)l * ntensors + t]) return false;
+        if (x.numel() != host_numel[t]) return false;
+        const at::ScalarType st = x.scalar_type();
+        if (st != at::kFloat && st != at::kHalf && st != at::kBFloat16) return false;
+        if (dt_code(st) != dtypes[l]) return false;
+      }
     }
     return true;
   }

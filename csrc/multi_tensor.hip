@@ -73,7 +73,9 @@ __device__ __forceinline__ void stream_for(const MTMeta& m, int64_t n, Body&& bo
   for (int64_t j = nv + threadIdx.x; j < n; j += kBlock) body(IG<1>{}, IG<1>{}, j, 0);
 }
 
-__device__ __forceinline__ float read_scale(const float* p, float v) { return p ? *p : v; }
+// The device scale (amp's inverse loss scale) and the host factor (1.0, or FusedAdam's legacy
+// scale / clip) both apply; callers without a host factor pass 1.0, which changes no bit.
+__device__ __forceinline__ float read_scale(const float* p, float v) { return p ? *p * v : v; }
 
 static inline int grid_for(int nchunks) {
   return nchunks < kMaxGrid ? (nchunks > 0 ? nchunks : 1) : kMaxGrid;
@@ -102,6 +104,17 @@ __global__ void __launch_bounds__(kBlock) scale_kernel(MTMeta m, const float* sp
         for (int k = 0; k < NE; ++k) {
           bad |= !__builtin_isfinite(x[u][k]);
           x[u][k] *= s;
+          // fp16 out: keep the fp32 product a rounding step of its own. Left alone, the scalar
+          // sweep fuses multiply and conversion (v_fma_mixlo_f16, one rounding of the exact
+          // product) while the vector sweep converts the fp32 product (v_cvt_pk_f16_f32), and
+          // the same element gets different bits on the two paths when that product is a tie.
+          // The barrier rests on the backend's present instruction choice; what holds it in place
+          // is tests/test_multi_tensor_gpu.py::test_scale_is_bit_identical_on_every_path. The other
+          // fp16 outputs of this file (axpby's result, the optimizers' fp16 copies) have no such
+          // barrier and may convert through v_fma_mix*: axpby is specified to one rounding of the
+          // exact result only, and the copies are held to "fp32 master rounded once" by the
+          // exact-copy tests there.
+          if constexpr (std::is_same<TO, f16>::value) asm("" : "+v"(x[u][k]));
         }
 #pragma unroll
       for (int u = 0; u < NG; ++u) store_f<TO, NE>(out + j0 + u * st, x[u]);
