@@ -1,7 +1,10 @@
 """Attention core used by apex.contrib.multihead_attn and the model zoo (NS-05).
 
 ``attention_packed(qkv[B,S,3,h,d], bias, p, causal, scale, k_lens) -> [B,S,h,d]`` and
-``attention(q, k, v, ...)`` for separate [B, S, h, d] views.
+``attention(q, k, v, ...)`` for separate [B, S, h, d] views. Grouped-query attention: ``attention``
+takes k / v with hk < h heads (h % hk == 0), and ``attention_grouped_packed(qkv[B,S,h+2hk,d], h, hk,
+...)`` the packed projection output (query heads, then key heads, then value heads); the flash
+kernels read each K/V head once per query head of its group, nothing is expanded.
 
 Every bf16/fp16 device call runs the MFMA flash-attention kernels in apex._C
 (csrc/attention_impl.h):
@@ -95,8 +98,10 @@ def prepare_bias(bias, B, H, Sq, Sk, dtype):
 
 
 def attention_reference(q, k, v, attn_bias=None, dropout_p=0.0, causal=False, scale=None, k_lens=None):
-    """q: [B, Sq, h, d], k/v: [B, Sk, h, d] -> [B, Sq, h, d] (fp32 softmax statistics)."""
+    """q: [B, Sq, h, d], k/v: [B, Sk, h, d] -> [B, Sq, h, d] (fp32 softmax statistics). k / v with
+    hk < h heads (grouped-query attention) are expanded group-wise first."""
     B, Sq, H, d = q.shape
+    k, v = _expand_kv(q, k, v)
     Sk = k.shape[1]
     scale = 1.0 / math.sqrt(d) if scale is None else scale
     s = torch.einsum("bqhd,bkhd->bhqk", q.float(), k.float()) * scale
@@ -114,6 +119,23 @@ def attention_reference(q, k, v, attn_bias=None, dropout_p=0.0, causal=False, sc
     if dropout_p > 0:
         p = F.dropout(p, dropout_p, True)
     return torch.einsum("bhqk,bkhd->bqhd", p, v.float()).to(q.dtype)
+
+
+def _check_groups(H, Hk):
+    if Hk != H and (Hk < 1 or H % Hk):
+        raise ValueError(f"grouped-query attention needs the {H} query heads to be a multiple of the "
+                         f"{Hk} key/value heads")
+
+
+def _expand_kv(q, k, v):
+    """Grouped-query K/V ([B, Sk, hk, d], hk a divisor of q's h) expanded to one head per query head,
+    for the paths that do not reach the flash kernels; autograd sums the gradient over each group."""
+    H, Hk = q.shape[2], k.shape[2]
+    _check_groups(H, Hk)
+    if Hk == H:
+        return k, v
+    g = H // Hk
+    return k.repeat_interleave(g, dim=2), v.repeat_interleave(g, dim=2)
 
 
 def _pad_last(t, n):
@@ -157,9 +179,36 @@ def _fallback(q, k, v, attn_bias, dropout_p, causal, scale, k_lens):
     return attention_reference(q, k, v, attn_bias, dropout_p, causal, scale, k_lens)
 
 
+def attention_grouped_packed(qkv, num_heads, num_kv_heads, attn_bias=None, dropout_p=0.0, causal=False,
+                             scale=None, k_lens=None):
+    """Grouped-query attention on the packed projection output ``qkv [B, S, H + 2 Hk, d]`` (the H query
+    heads, then the Hk key heads, then the Hk value heads) -> [B, S, H, d]."""
+    H, Hk = int(num_heads), int(num_kv_heads)
+    _check_groups(H, Hk)
+    if qkv.dim() != 4 or qkv.shape[2] != H + 2 * Hk:
+        raise ValueError(f"qkv must be [B, S, num_heads + 2 * num_kv_heads, d], got {tuple(qkv.shape)} for "
+                         f"{H} / {Hk} heads")
+    B, S, _, d = qkv.shape
+    scale = 1.0 / math.sqrt(d) if scale is None else scale
+    if _native_ok(qkv, attn_bias):
+        from . import flash
+
+        bias = prepare_bias(attn_bias, B, H, S, S, qkv.dtype)
+        dp = _padded_dim(d)
+        if dp == d:
+            return flash.flash_attention_grouped_packed(qkv, H, Hk, dropout_p, causal, scale, k_lens, bias)
+        o = flash.flash_attention_grouped_packed(_pad_last(qkv, dp), H, Hk, dropout_p, causal, scale, k_lens, bias)
+        return o[..., :d]
+    q, k, v = qkv[:, :, :H], qkv[:, :, H:H + Hk], qkv[:, :, H + Hk:]
+    k, v = _expand_kv(q, k, v)
+    return _fallback(q, k, v, attn_bias, dropout_p, causal, scale, k_lens)
+
+
 def attention(q, k, v, attn_bias=None, dropout_p=0.0, causal=False, scale=None, k_lens=None):
-    """q: [B, Sq, h, d], k/v: [B, Sk, h, d] -> [B, Sq, h, d]."""
+    """q: [B, Sq, h, d], k/v: [B, Sk, hk, d] -> [B, Sq, h, d]; hk == h, or a divisor of it for
+    grouped-query attention (query heads [j h/hk, (j + 1) h/hk) attend to K/V head j)."""
     B, Sq, h, d = q.shape
+    _check_groups(h, k.shape[2])
     scale = 1.0 / math.sqrt(d) if scale is None else scale
     if _native_ok(q, attn_bias):
         from . import flash
@@ -171,4 +220,5 @@ def attention(q, k, v, attn_bias=None, dropout_p=0.0, causal=False, scale=None, 
         o = flash.flash_attention(_pad_last(q, dp), _pad_last(k, dp), _pad_last(v, dp), dropout_p, causal, scale,
                                   k_lens, bias)
         return o[..., :d]
+    k, v = _expand_kv(q, k, v)
     return _fallback(q, k, v, attn_bias, dropout_p, causal, scale, k_lens)

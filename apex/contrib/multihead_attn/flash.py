@@ -31,7 +31,8 @@ def _dbias_out(dbias, bias):
 
 
 class FlashAttnFunc(torch.autograd.Function):
-    """q, k, v: [B, S, H, D] views (D contiguous) -> o [B, Sq, H, D]; ``bias``: optional additive
+    """q: [B, Sq, H, D], k / v: [B, Sk, Hk, D] views (D contiguous), Hk == H or a divisor of it
+    (grouped-query: query heads [j H/Hk, (j + 1) H/Hk) read K/V head j) -> o [B, Sq, H, D]; ``bias``: optional additive
     score bias (apex.contrib.multihead_attn.attention.prepare_bias layout); when it requires a
     gradient the backward returns dS reduced to its shape."""
 
@@ -91,6 +92,63 @@ class FlashAttnPackedFunc(torch.autograd.Function):
         return dqkv, None, None, None, None, _dbias_out(dbias, bias)
 
 
+def _kv_groups(H, Hk):
+    if Hk < 1 or H % Hk:
+        raise ValueError(f"grouped-query attention needs the {H} query heads to be a multiple of the "
+                         f"{Hk} key/value heads")
+    return H // Hk
+
+
+def _split_grouped(qkv, H, Hk):
+    """The Q, K and V views of ``[B, S, H + 2 Hk, D]`` (same strides, no copy)."""
+    return qkv[:, :, :H], qkv[:, :, H:H + Hk], qkv[:, :, H + Hk:]
+
+
+class FlashAttnGroupedPackedFunc(torch.autograd.Function):
+    """qkv: [B, S, H + 2 Hk, D] — the H query heads, then the Hk key heads, then the Hk value heads on
+    one head axis (the grouped QKV projection output, consumed in place). Query heads
+    [j H/Hk, (j + 1) H/Hk) attend to K/V head j. The gradient is produced directly in that layout:
+    the kernels write dQ into its slice and the group reduction writes dK / dV into theirs (no cat)."""
+
+    @staticmethod
+    def forward(ctx, qkv, num_heads, num_kv_heads, dropout_p, causal, scale, k_lens, bias=None):
+        C = _ext.require()
+        q, k, v = _split_grouped(qkv, num_heads, num_kv_heads)
+        seed, offset = _seed_pair(dropout_p, qkv.device)
+        o, lse, dmask = C.flash_attn_fwd(q, k, v, bool(causal), float(scale), float(dropout_p), seed, offset,
+                                         k_lens, bias)
+        ctx.save_for_backward(qkv, o, lse, k_lens, dmask, bias)
+        ctx.cfg = (num_heads, num_kv_heads, dropout_p, causal, scale, seed, offset)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        C = _ext.require()
+        qkv, o, lse, k_lens, dmask, bias = ctx.saved_tensors
+        H, Hk, p, causal, scale, seed, offset = ctx.cfg
+        if do.stride(-1) != 1 or do.stride(1) % 8 or do.stride(0) % 8 or do.stride(2) % 8:
+            do = do.contiguous()
+        q, k, v = _split_grouped(qkv, H, Hk)
+        dqkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
+        dq, dk, dv = _split_grouped(dqkv, H, Hk)
+        dbias = _dbias_buffer(ctx, bias, 7)
+        C.flash_attn_bwd(do, q, k, v, o, lse, dq, dk, dv, bool(causal), float(scale), float(p), seed,
+                         offset, k_lens, dmask, None, 0, bias, dbias=dbias)
+        return dqkv, None, None, None, None, None, None, _dbias_out(dbias, bias)
+
+
+def flash_attention_grouped_packed(qkv, num_heads, num_kv_heads, dropout_p=0.0, causal=False, scale=None,
+                                   k_lens=None, bias=None):
+    _kv_groups(num_heads, num_kv_heads)
+    if qkv.dim() != 4 or qkv.shape[2] != num_heads + 2 * num_kv_heads:
+        raise ValueError(f"qkv must be [B, S, num_heads + 2 * num_kv_heads, D], got {tuple(qkv.shape)} for "
+                         f"{num_heads} / {num_kv_heads} heads")
+    d = qkv.shape[-1]
+    scale = 1.0 / math.sqrt(d) if scale is None else scale
+    return FlashAttnGroupedPackedFunc.apply(qkv, int(num_heads), int(num_kv_heads), float(dropout_p), bool(causal),
+                                            float(scale), k_lens, bias)
+
+
 def flash_attention_packed(qkv, dropout_p=0.0, causal=False, scale=None, k_lens=None, bias=None):
     d = qkv.shape[-1]
     scale = 1.0 / math.sqrt(d) if scale is None else scale
@@ -98,6 +156,9 @@ def flash_attention_packed(qkv, dropout_p=0.0, causal=False, scale=None, k_lens=
 
 
 def flash_attention(q, k, v, dropout_p=0.0, causal=False, scale=None, k_lens=None, bias=None):
+    """k / v may hold fewer heads than q ([B, Sk, Hk, D], H % Hk == 0): grouped-query attention."""
+    if k.shape[2] != q.shape[2]:
+        _kv_groups(q.shape[2], k.shape[2])
     d = q.shape[-1]
     scale = 1.0 / math.sqrt(d) if scale is None else scale
     return FlashAttnFunc.apply(q, k, v, float(dropout_p), bool(causal), float(scale), k_lens, bias)

@@ -41,8 +41,11 @@ class GPTConfig:
     position_embedding_type: str = "learned"  # "learned" | "rope"
     rotary_percent: float = 1.0
     rotary_base: int = 10000
+    n_kv_head: int | None = None  # grouped-query attention: key/value heads (None = n_head)
 
     def __post_init__(self):
+        if self.n_kv_head is not None and (self.n_kv_head < 1 or self.n_head % self.n_kv_head):
+            raise ValueError(f"n_head={self.n_head} must be a multiple of n_kv_head={self.n_kv_head}")
         if self.position_embedding_type not in ("learned", "rope"):
             raise ValueError(f"position_embedding_type must be 'learned' or 'rope', got "
                              f"{self.position_embedding_type!r}")
@@ -70,7 +73,10 @@ class GPTBlock(nn.Module):
         super().__init__()
         self.h, self.d = c.n_head, c.n_embd // c.n_head
         self.ln_1 = FusedLayerNorm(c.n_embd, eps=c.layer_norm_eps)
-        self.c_attn = nn.Linear(c.n_embd, 3 * c.n_embd)
+        # grouped-query attention (hk < h): c_attn emits the h query heads, then hk key heads, then hk
+        # value heads; hk == h keeps the [3, h, d] packed layout
+        self.hk = c.n_head if c.n_kv_head is None else c.n_kv_head
+        self.c_attn = nn.Linear(c.n_embd, 3 * c.n_embd if self.hk == self.h else (self.h + 2 * self.hk) * self.d)
         self.c_proj = nn.Linear(c.n_embd, c.n_embd)
         self.ln_2 = FusedLayerNorm(c.n_embd, eps=c.layer_norm_eps)
         self.c_fc = nn.Linear(c.n_embd, 4 * c.n_embd)
@@ -83,12 +89,22 @@ class GPTBlock(nn.Module):
         # sublayer does not use (QKV GEMM, this rotation and the flash kernel are separate ops).
         return qkv if rope is None else fused_rope.apply_rotary_qkv_packed(qkv, rope[0], rope[1])
 
+    def _attn_grouped(self, xn, rope, p):
+        B, S, E = xn.shape
+        qkv = fops.fused_dense(xn, self.c_attn.weight, self.c_attn.bias).view(B, S, self.h + 2 * self.hk, self.d)
+        if rope is not None:
+            qkv = fused_rope.apply_rotary_qkv_grouped(qkv, rope[0], rope[1], self.h, self.hk)
+        return fops.attention_qkv_grouped(qkv, self.h, self.hk, None, p, causal=True).reshape(B, S, E)
+
     def forward(self, x, rope=None):
         B, S, E = x.shape
         p = self.p if self.training else 0.0
-        qkv = fops.fused_dense(self.ln_1(x), self.c_attn.weight, self.c_attn.bias).view(B, S, 3, self.h, self.d)
-        qkv = self._rotate(qkv, rope)
-        ctx = fops.attention_qkv_packed(qkv, None, p, causal=True).reshape(B, S, E)
+        if self.hk != self.h:
+            ctx = self._attn_grouped(self.ln_1(x), rope, p)
+        else:
+            qkv = fops.fused_dense(self.ln_1(x), self.c_attn.weight, self.c_attn.bias).view(B, S, 3, self.h, self.d)
+            qkv = self._rotate(qkv, rope)
+            ctx = fops.attention_qkv_packed(qkv, None, p, causal=True).reshape(B, S, E)
         x = fops.bias_dropout_add(fops.fused_dense(ctx, self.c_proj.weight, None), self.c_proj.bias, x, p)
         xn = self.ln_2(x)
         t = fblocks.mlp(xn, self.c_fc.weight, self.c_fc.bias, self.mlp_proj.weight, fops.ACT_GELU_TANH)
@@ -105,9 +121,12 @@ class GPTBlock(nn.Module):
         two gradients are summed inside the LayerNorm backward."""
         B, S, E = x.shape
         p = self.p if self.training else 0.0
-        qkv = fops.fused_dense(xn, self.c_attn.weight, self.c_attn.bias).view(B, S, 3, self.h, self.d)
-        qkv = self._rotate(qkv, rope)
-        ctx = fops.attention_qkv_packed(qkv, None, p, causal=True).reshape(B, S, E)
+        if self.hk != self.h:
+            ctx = self._attn_grouped(xn, rope, p)
+        else:
+            qkv = fops.fused_dense(xn, self.c_attn.weight, self.c_attn.bias).view(B, S, 3, self.h, self.d)
+            qkv = self._rotate(qkv, rope)
+            ctx = fops.attention_qkv_packed(qkv, None, p, causal=True).reshape(B, S, E)
         x, xn = fops.bias_dropout_add_ln(fops.fused_dense(ctx, self.c_proj.weight, None), self.c_proj.bias, x,
                                          self.ln_2.weight, self.ln_2.bias, p, self.ln_2.eps)
         t = fblocks.mlp(xn, self.c_fc.weight, self.c_fc.bias, self.mlp_proj.weight, fops.ACT_GELU_TANH)

@@ -48,8 +48,13 @@ class MegatronGPTConfig:
     position_embedding_type: str = "learned"  # "learned" | "rope"
     rotary_percent: float = 1.0
     rotary_base: int = 10000
+    num_query_groups: int | None = None  # grouped-query attention: key/value heads (None = num_attention_heads)
 
     def __post_init__(self):
+        g = self.num_query_groups
+        if g is not None and (g < 1 or self.num_attention_heads % g):
+            raise ValueError(f"num_attention_heads={self.num_attention_heads} must be a multiple of "
+                             f"num_query_groups={g}")
         if self.ffn_hidden_size is None:
             self.ffn_hidden_size = 4 * self.hidden_size
         if self.position_embedding_type not in ("learned", "rope"):
@@ -81,7 +86,14 @@ class ParallelTransformerLayer(nn.Module):
         self.d = c.hidden_size // c.num_attention_heads
         out_std = c.init_method_std / math.sqrt(2.0 * c.num_layers)
         self.input_layernorm = FusedLayerNorm(c.hidden_size, eps=c.layernorm_epsilon)
-        self.query_key_value = tp.ColumnParallelLinear(c.hidden_size, 3 * c.hidden_size, gather_output=False,
+        # grouped-query attention: every rank's shard of query_key_value is laid out rank-locally as its
+        # query heads, then its key heads, then its value heads ([3, heads_local, d] when groups == heads)
+        groups = c.num_attention_heads if c.num_query_groups is None else c.num_query_groups
+        if groups % tpws:
+            raise ValueError(f"num_query_groups={groups} must be a multiple of the tensor-parallel world size {tpws}")
+        self.groups_local = groups // tpws
+        qkv_out = 3 * c.hidden_size if groups == c.num_attention_heads else (c.num_attention_heads + 2 * groups) * self.d
+        self.query_key_value = tp.ColumnParallelLinear(c.hidden_size, qkv_out, gather_output=False,
                                                        init_method=_init(c.init_method_std),
                                                        params_dtype=c.params_dtype)
         self.dense = tp.RowParallelLinear(c.hidden_size, c.hidden_size, input_is_parallel=True,
@@ -102,14 +114,25 @@ class ParallelTransformerLayer(nn.Module):
         # not use (QKV GEMM, this rotation and the flash kernel are separate bf16 / fp16 ops).
         return qkv if rope is None else fused_rope.apply_rotary_qkv_packed(qkv, rope[0], rope[1])
 
+    def _attn(self, qkv, rope, pa):
+        B, S = qkv.shape[:2]
+        h, hk = self.heads_local, self.groups_local
+        if hk != h:
+            qkv = qkv.view(B, S, h + 2 * hk, self.d)
+            if rope is not None:
+                qkv = fused_rope.apply_rotary_qkv_grouped(qkv, rope[0], rope[1], h, hk)
+            with _tp_rng():
+                return fops.attention_qkv_grouped(qkv, h, hk, None, pa, causal=True)
+        qkv = self._rotate(qkv.view(B, S, 3, self.heads_local, self.d), rope)
+        with _tp_rng():
+            return fops.attention_qkv_packed(qkv, None, pa, causal=True)
+
     def forward(self, x, rope=None):
         B, S, _ = x.shape
         ph = self.p_hidden if self.training else 0.0
         pa = self.p_attn if self.training else 0.0
         qkv, _ = self.query_key_value(self.input_layernorm(x))
-        qkv = self._rotate(qkv.view(B, S, 3, self.heads_local, self.d), rope)
-        with _tp_rng():
-            ctx = fops.attention_qkv_packed(qkv, None, pa, causal=True)
+        ctx = self._attn(qkv, rope, pa)
         out, bias = self.dense(ctx.reshape(B, S, -1))
         x = fops.bias_dropout_add(out, bias, x, ph)
         xn = self.post_attention_layernorm(x)
@@ -134,9 +157,7 @@ class ParallelTransformerLayer(nn.Module):
         ph = self.p_hidden if self.training else 0.0
         pa = self.p_attn if self.training else 0.0
         qkv, _ = self.query_key_value(xn)
-        qkv = self._rotate(qkv.view(B, S, 3, self.heads_local, self.d), rope)
-        with _tp_rng():
-            ctx = fops.attention_qkv_packed(qkv, None, pa, causal=True)
+        ctx = self._attn(qkv, rope, pa)
         out, bias = self.dense(ctx.reshape(B, S, -1))
         ln2 = self.post_attention_layernorm
         x, xn = fops.bias_dropout_add_ln(out, bias, x, ln2.weight, ln2.bias, ph, ln2.eps)

@@ -12,7 +12,7 @@ the PyTorch reference formulation on CPU (also the numerics reference for the te
                                             y = LN(res + dropout(x W^T + b))  (one fused
                                                                      kernel each way)
   bias_dropout_add(x, b, res, p)            y = res + dropout(x + b)
-  attention_qkv_packed / softmax_cross_entropy
+  attention_qkv_packed / attention_qkv_grouped / softmax_cross_entropy
 
 Forward and input-gradient GEMMs run on the hand-written MFMA kernel (apex.ops.gemm, with
 bias / bias+GELU in its epilogue where it applies); weight gradients are hipBLASLt with split-K.
@@ -262,6 +262,15 @@ def attention_qkv_packed(qkv, attn_bias=None, dropout_p=0.0, causal=False, scale
     from ..contrib.multihead_attn import attention as _attn
 
     return _attn.attention_packed(qkv, attn_bias, dropout_p, causal, scale, k_lens)
+
+
+def attention_qkv_grouped(qkv, num_heads, num_kv_heads, attn_bias=None, dropout_p=0.0, causal=False, scale=None,
+                          k_lens=None):
+    """Grouped-query attention. qkv: [B, S, H + 2 Hk, d] (the H query heads, then the Hk key heads, then
+    the Hk value heads; query heads [j H/Hk, (j + 1) H/Hk) attend to K/V head j) -> context [B, S, H, d]."""
+    from ..contrib.multihead_attn import attention as _attn
+
+    return _attn.attention_grouped_packed(qkv, num_heads, num_kv_heads, attn_bias, dropout_p, causal, scale, k_lens)
 
 
 def softmax_cross_entropy(logits, labels, ignore_index=-100, smoothing=0.0, reduction="mean"):

@@ -442,12 +442,20 @@ class _RingAttention(torch.autograd.Function):
         return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype), None, None, None, None, None, None, None
 
 
+def _require_same_heads(q, k, v, what):
+    if k.shape[2] != q.shape[2] or v.shape[2] != q.shape[2]:
+        raise NotImplementedError(f"{what} does not support grouped-query attention: q has {q.shape[2]} heads, "
+                                  f"k / v have {k.shape[2]} / {v.shape[2]}; expand k / v to one head per "
+                                  f"query head (repeat_interleave on dim 2) first")
+
+
 def ring_attention(q, k, v, group=None, causal=False, scale=None, dropout_p=0.0, layout="zigzag"):
     """Attention of this rank's query shard over the whole (sharded) key sequence.
 
     q, k, v: [B, S_local, H, D] shards laid out by ``shard_sequence(..., layout)``; returns this
     rank's [B, S_local, H, D] output shard. ``group``: the CP group (default: parallel_state's).
     """
+    _require_same_heads(q, k, v, "ring_attention")
     g, W, r, ranks = _group_info(group)
     scale = 1.0 / math.sqrt(q.shape[-1]) if scale is None else float(scale)
     if W == 1:
@@ -508,6 +516,7 @@ def ulysses_attention(q, k, v, group=None, causal=False, scale=None, dropout_p=0
     apex.contrib.multihead_attn's (flash kernels on device)."""
     from ..contrib.multihead_attn.attention import attention
 
+    _require_same_heads(q, k, v, "ulysses_attention")
     g, W, _, _ = _group_info(group)
     if W == 1:
         return attention(q, k, v, dropout_p=dropout_p, causal=causal, scale=scale, k_lens=k_lens)

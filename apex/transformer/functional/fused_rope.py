@@ -9,7 +9,8 @@ Upstream-compatible entry points (non-interleaved "rotate half" pairing):
 
 and the project-native ``apply_rotary_qkv_packed(qkv[B, S, 3, h, d], cos[S, d2], sin[S, d2])`` the
 GPT models call between the QKV projection and the packed flash attention: one launch rotates Q
-and K and copies V into a new packed tensor.
+and K and copies V into a new packed tensor; ``apply_rotary_qkv_grouped(qkv[B, S, H + 2 Hk, d], cos,
+sin, H, Hk)`` is its grouped-query form (Q heads, then K heads, then V heads on one head axis).
 
 One stride-generic kernel serves all of them: the tensor is handed over as an ``[S, B, H, D]`` view
 (any seq / batch / head strides, D contiguous), the rotation is read from fp32-computed cos / sin
@@ -29,7 +30,8 @@ import torch
 from ... import _ext
 
 __all__ = ["fused_apply_rotary_pos_emb", "fused_apply_rotary_pos_emb_cached", "fused_apply_rotary_pos_emb_thd",
-           "apply_rotary_qkv_packed", "RotaryEmbedding", "rope_reference", "rope_reference_qkv_packed"]
+           "apply_rotary_qkv_packed", "apply_rotary_qkv_grouped", "RotaryEmbedding", "rope_reference",
+           "rope_reference_qkv_packed", "rope_reference_qkv_grouped"]
 
 _KERNEL_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 
@@ -90,6 +92,13 @@ def rope_reference_qkv_packed(qkv, cos, sin):
     B, S, three, h, d = qkv.shape
     t4 = qkv.reshape(B, S, 3 * h, d).transpose(0, 1)
     return _rotate(t4, cos, sin, rot_heads=2 * h).transpose(0, 1).reshape(B, S, 3, h, d)
+
+
+def rope_reference_qkv_grouped(qkv, cos, sin, num_heads, num_kv_heads):
+    """Eager composition of :func:`apply_rotary_qkv_grouped`: the Q and K heads rotated, V passed through."""
+    _grouped_heads(qkv, num_heads, num_kv_heads)
+    cos, sin = _tables(cos, sin)
+    return _rotate(qkv.transpose(0, 1), cos, sin, rot_heads=num_heads + num_kv_heads).transpose(0, 1)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -177,26 +186,32 @@ class _FusedRoPETHD(torch.autograd.Function):
 
 
 class _FusedRoPEQKVPacked(torch.autograd.Function):
+    """Packed QKV, ``[B, S, 3, h, d]`` or grouped ``[B, S, heads, d]``: the first ``rot_heads`` heads of
+    the flattened head axis are rotated, the rest (V) copied."""
+
     @staticmethod
-    def _run(x, cos, sin, backward):
-        B, S, _, h, d = x.shape
-        if x.stride(-1) != 1 or x.stride(2) != h * x.stride(3):  # (3, h) must flatten to one head axis
+    def _run(x, cos, sin, rot_heads, backward):
+        B, S, d = x.shape[0], x.shape[1], x.shape[-1]
+        # a packed (3, h) pair must flatten to one head axis
+        if x.stride(-1) != 1 or (x.dim() == 5 and x.stride(2) != x.shape[3] * x.stride(3)):
             x = x.contiguous()
+        heads = x.shape[2] * x.shape[3] if x.dim() == 5 else x.shape[2]
         out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-        x4 = x.as_strided((S, B, 3 * h, d), (x.stride(1), x.stride(0), x.stride(3), 1), x.storage_offset())
-        _launch(x4, out.view(B, S, 3 * h, d).transpose(0, 1), cos, sin, None, 2 * h, backward)
+        x4 = x.as_strided((S, B, heads, d), (x.stride(1), x.stride(0), x.stride(-2), 1), x.storage_offset())
+        _launch(x4, out.view(B, S, heads, d).transpose(0, 1), cos, sin, None, rot_heads, backward)
         return out
 
     @staticmethod
-    def forward(ctx, qkv, cos, sin):
+    def forward(ctx, qkv, cos, sin, rot_heads):
         ctx.save_for_backward(cos, sin)
-        return _FusedRoPEQKVPacked._run(qkv, cos, sin, False)
+        ctx.rot_heads = rot_heads
+        return _FusedRoPEQKVPacked._run(qkv, cos, sin, rot_heads, False)
 
     @staticmethod
     def backward(ctx, dy):
         # out of place: the incoming gradient may be shared with other consumers; dV is copied
         cos, sin = ctx.saved_tensors
-        return _FusedRoPEQKVPacked._run(dy, cos, sin, True), None, None
+        return _FusedRoPEQKVPacked._run(dy, cos, sin, ctx.rot_heads, True), None, None, None
 
 
 # ----------------------------------------------------------------------------------------------
@@ -241,7 +256,25 @@ def apply_rotary_qkv_packed(qkv, cos, sin):
         raise ValueError(f"qkv must be [B, S, 3, h, d], got {tuple(qkv.shape)}")
     cos, sin = _tables(cos, sin)
     _check(qkv.transpose(0, 1), cos, sin, dense=True)
-    return _FusedRoPEQKVPacked.apply(qkv, cos.detach(), sin.detach())
+    return _FusedRoPEQKVPacked.apply(qkv, cos.detach(), sin.detach(), 2 * qkv.shape[3])
+
+
+def _grouped_heads(qkv, num_heads, num_kv_heads):
+    if qkv.dim() != 4 or num_kv_heads < 1 or num_heads % num_kv_heads or \
+            qkv.shape[2] != num_heads + 2 * num_kv_heads:
+        raise ValueError(f"qkv must be [B, S, num_heads + 2 * num_kv_heads, d] with num_heads a multiple of "
+                         f"num_kv_heads, got {tuple(qkv.shape)} for {num_heads} / {num_kv_heads} heads")
+
+
+def apply_rotary_qkv_grouped(qkv, cos, sin, num_heads, num_kv_heads):
+    """Grouped-query form of :func:`apply_rotary_qkv_packed`: ``qkv [B, S, H + 2 Hk, d]`` holds the ``H``
+    query heads, then the ``Hk`` key heads, then the ``Hk`` value heads. Heads ``[0, H + Hk)`` are
+    rotated by the ``[S, d2]`` tables and the V heads copied, in one launch, into a new tensor of the
+    same layout (out of place; so is the backward)."""
+    _grouped_heads(qkv, num_heads, num_kv_heads)
+    cos, sin = _tables(cos, sin)
+    _check(qkv.transpose(0, 1), cos, sin, dense=True)
+    return _FusedRoPEQKVPacked.apply(qkv, cos.detach(), sin.detach(), num_heads + num_kv_heads)
 
 
 class RotaryEmbedding(torch.nn.Module):

@@ -160,8 +160,9 @@ __global__ void __launch_bounds__(256) attn_f32_fwd_kernel(AttnArgs a) {
   const int qw = q0 + 32 * wid;  // this wave's first query
   const int qrow = qw + r;
   const int Sk = a.k_lens ? min(a.k_lens[b], a.Sk) : a.Sk;
-  const float* kp = (const float*)a.k + b * a.k_bs + h * a.k_hs;
-  const float* vp = (const float*)a.v + b * a.v_bs + h * a.v_hs;
+  const int hk = a.kv_group > 1 ? h / a.kv_group : h;  // grouped-query: the K/V head of query head h
+  const float* kp = (const float*)a.k + b * a.k_bs + hk * a.k_hs;
+  const float* vp = (const float*)a.v + b * a.v_bs + hk * a.v_hs;
   const float* brow = BIAS ? bias_row<float>(a, b, h, qrow) : nullptr;
 
   float qf[D / 2];  // scale * Q[qrow][d(s, half)]
@@ -275,8 +276,9 @@ __global__ void __launch_bounds__(256) attn_f32_bwd_dkdv_kernel(AttnArgs a, cons
   const float* bcol = BIAS ? (const float*)a.bias + b * a.bias_bs + h * a.bias_hs + min(key, a.Sk - 1) : nullptr;
 
   float kf[D / 2], vf[D / 2];
-  row_regs<D>((const float*)a.k + b * a.k_bs + h * a.k_hs + (int64_t)key * a.k_ss, key < Sk, hl, 1.f, kf);
-  row_regs<D>((const float*)a.v + b * a.v_bs + h * a.v_hs + (int64_t)key * a.v_ss, key < Sk, hl, 1.f, vf);
+  const int hk = a.kv_group > 1 ? h / a.kv_group : h;  // grouped-query: the K/V head of query head h
+  row_regs<D>((const float*)a.k + b * a.k_bs + hk * a.k_hs + (int64_t)key * a.k_ss, key < Sk, hl, 1.f, kf);
+  row_regs<D>((const float*)a.v + b * a.v_bs + hk * a.v_hs + (int64_t)key * a.v_ss, key < Sk, hl, 1.f, vf);
   f32x16 dkt[D / 32], dvt[D / 32];
 #pragma unroll
   for (int i = 0; i < D / 32; ++i) dkt[i] = dvt[i] = f32x16{};
@@ -381,8 +383,9 @@ __global__ void __launch_bounds__(256) attn_f32_bwd_dq_kernel(AttnArgs a, const 
   const int qrow = qw + r;
   const bool qok = qrow < a.Sq;
   const int Sk = a.k_lens ? min(a.k_lens[b], a.Sk) : a.Sk;
-  const float* kp = (const float*)a.k + b * a.k_bs + h * a.k_hs;
-  const float* vp = (const float*)a.v + b * a.v_bs + h * a.v_hs;
+  const int hk = a.kv_group > 1 ? h / a.kv_group : h;  // grouped-query: the K/V head of query head h
+  const float* kp = (const float*)a.k + b * a.k_bs + hk * a.k_hs;
+  const float* vp = (const float*)a.v + b * a.v_bs + hk * a.v_hs;
   const float* brow = BIAS ? bias_row<float>(a, b, h, qrow) : nullptr;
 
   float qf[D / 2], dof[D / 2];

@@ -291,9 +291,10 @@ attn_fwd_kernel(AttnArgs a) {
   // BIAS: scores are taken to the natural domain s' = s * scale + bias, so the exp2 factor is log2(e)
   const float sl2 = BIAS ? kLog2e : a.scale_log2;
 
+  const int hk = a.kv_group > 1 ? h / a.kv_group : h;  // grouped-query: the K/V head of query head h
   const T* qp = (const T*)a.q + b * a.q_bs + h * a.q_hs;
-  const T* kp = (const T*)a.k + b * a.k_bs + h * a.k_hs;
-  const T* vp = (const T*)a.v + b * a.v_bs + h * a.v_hs;
+  const T* kp = (const T*)a.k + b * a.k_bs + hk * a.k_hs;
+  const T* vp = (const T*)a.v + b * a.v_bs + hk * a.v_hs;
   const T* brow = BIAS ? bias_row<T>(a, b, h, qrow) : nullptr;
   // fp8 codes of O: scale and the amax filter value read here, their latency under the main loop
   const float q8s = a.q8o ? a.q8_scale[0] : 0.f, q8seen = a.q8o ? f8_amax_seen(a.q8_amax) : 0.f;
@@ -684,9 +685,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D <= 6
   const int mykey = k0 + 32 * wid + r;  // key row this lane holds as K/V operand
 
   const T* qp = (const T*)a.q + b * a.q_bs + h * a.q_hs;
-  const T* kp = (const T*)a.k + b * a.k_bs + h * a.k_hs;
-  const T* vp = (const T*)a.v + b * a.v_bs + h * a.v_hs;
-  const T* dop = (const T*)dout + b * a.do_bs + h * a.do_hs;
+  const int hk = a.kv_group > 1 ? h / a.kv_group : h;  // grouped-query: the K/V head of query head h
+  const T* kp = (const T*)a.k + b * a.k_bs + hk * a.k_hs;
+  const T* vp = (const T*)a.v + b * a.v_bs + hk * a.v_hs;
+  const T* dop =(const T*)dout + b * a.do_bs + h * a.do_hs;
   const T* op = (const T*)a.o + b * a.o_bs + h * a.o_hs;
   const float* lsep = a.lse + (int64_t)bh * a.Sq;
   const float* dlp = DQ ? nullptr : delta_in + (int64_t)bh * a.Sq;
@@ -1216,8 +1218,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D <= 6
 
   const T* qp = (const T*)a.q + b * a.q_bs + h * a.q_hs;
   const T* dop = (const T*)dout + b * a.do_bs + h * a.do_hs;
-  const T* kp = (const T*)a.k + b * a.k_bs + h * a.k_hs;
-  const T* vp = (const T*)a.v + b * a.v_bs + h * a.v_hs;
+  const int hk = a.kv_group > 1 ? h / a.kv_group : h;  // grouped-query: the K/V head of query head h
+  const T* kp = (const T*)a.k + b * a.k_bs + hk * a.k_hs;
+  const T* vp = (const T*)a.v + b * a.v_bs + hk * a.v_hs;
   const T* brow = BIAS ? bias_row<T>(a, b, h, qrow) : nullptr;
 
   // Q^T and dO^T fragments (B operands): lane (q=r, hl) holds X[q][16s + 8hl .. +7]

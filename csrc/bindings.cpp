@@ -334,8 +334,12 @@ apex::AttnArgs attn_common(const Tensor& q, const Tensor& k, const Tensor& v, bo
   a.H = (int)q.size(2);
   a.D = (int)q.size(3);
   a.Sk = (int)k.size(1);
-  TORCH_CHECK(k.size(0) == a.B && k.size(2) == a.H && k.size(3) == a.D && v.sizes() == k.sizes(),
-              "k/v shape mismatch");
+  TORCH_CHECK(k.size(0) == a.B && k.size(3) == a.D && v.sizes() == k.sizes(), "k/v shape mismatch");
+  // grouped-query attention: Hk K/V heads, each shared by H / Hk consecutive query heads
+  const int64_t Hk = k.size(2);
+  TORCH_CHECK(Hk == a.H || (Hk >= 1 && a.H % Hk == 0), "k/v shape mismatch: ", Hk,
+              " K/V heads do not divide ", a.H, " query heads");
+  a.kv_group = Hk == a.H ? 1 : (int)(a.H / Hk);
   TORCH_CHECK(a.D == 32 || a.D == 64 || a.D == 128 || a.D == 256,
               "flash attention supports head dims 32, 64, 128, 256 (pad others)");
   TORCH_CHECK(q.scalar_type() != at::kFloat || a.D <= 128, "fp32 flash attention supports head dims up to 128");
@@ -424,6 +428,32 @@ std::vector<Tensor> flash_attn_fwd(Tensor q, Tensor k, Tensor v, bool causal, do
   return {o, lse, dmask};
 }
 
+// grouped-query backward: dk / dv [B, Sk, Hk, D] (any batch / seq / head strides) <- the sum of each
+// group of H / Hk consecutive heads of the contiguous per-query-head dk_x / dv_x [B, Sk, H, D]
+void attn_kv_group_reduce(const Tensor& dk_x, const Tensor& dv_x, Tensor dk, Tensor dv) {
+  TORCH_CHECK(dk_x.is_cuda() && dk_x.dim() == 4 && dk_x.is_contiguous() && dv_x.is_contiguous() &&
+                  dv_x.sizes() == dk_x.sizes(),
+              "attn_kv_group_reduce: dk_x / dv_x must be contiguous [B, Sk, H, D] device tensors");
+  const int64_t B = dk_x.size(0), Sk = dk_x.size(1), H = dk_x.size(2), D = dk_x.size(3);
+  TORCH_CHECK(dk.dim() == 4 && dv.sizes() == dk.sizes() && dk.size(0) == B && dk.size(1) == Sk && dk.size(3) == D &&
+                  dk.size(2) >= 1 && H % dk.size(2) == 0,
+              "attn_kv_group_reduce: dk / dv must be [B, Sk, Hk, D] with Hk a divisor of H");
+  for (const Tensor* t : {&dk_x, &dv_x, (const Tensor*)&dk, (const Tensor*)&dv})
+    TORCH_CHECK(t->scalar_type() == dk_x.scalar_type() && t->device() == dk_x.device(),
+                "attn_kv_group_reduce: dtype / device mismatch");
+  const int64_t piece = 16 / (int64_t)dk_x.element_size();  // elements per 16-byte piece
+  TORCH_CHECK(D % piece == 0, "attn_kv_group_reduce: head rows must be a multiple of 16 bytes");
+  for (const Tensor* t : {(const Tensor*)&dk, (const Tensor*)&dv})
+    TORCH_CHECK(t->stride(3) == 1 && t->stride(0) % piece == 0 && t->stride(1) % piece == 0 &&
+                    t->stride(2) % piece == 0 && ((uintptr_t)t->data_ptr() & 15) == 0,
+                "attn_kv_group_reduce: dk / dv rows must be D-contiguous and 16-byte aligned");
+  const int Hk = (int)dk.size(2);
+  check(apex::attn_kv_group_reduce(dk_x.data_ptr(), dv_x.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, Sk, Hk,
+                                   (int)(H / Hk), (int)D, dk.stride(0), dk.stride(1), dk.stride(2), dv.stride(0),
+                                   dv.stride(1), dv.stride(2), dt_code(dk_x.scalar_type()), cur_stream()),
+        "attn_kv_group_reduce");
+}
+
 // returns true when the fp8 codes of dq / dk / dv were written (q8_* given and the single-kernel
 // backward ran: Sk <= 128; longer key ranges compute dq in a separate kernel without codes)
 bool flash_attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor dq,
@@ -465,6 +495,26 @@ bool flash_attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor 
   attn_set(a, dq, a.dq_bs, a.dq_ss, a.dq_hs);
   attn_set(a, dk, a.dk_bs, a.dk_ss, a.dk_hs);
   attn_set(a, dv, a.dv_bs, a.dv_ss, a.dv_hs);
+  TORCH_CHECK(dq.sizes() == q.sizes() && dk.sizes() == k.sizes() && dv.sizes() == v.sizes() &&
+                  dq.scalar_type() == q.scalar_type() && dk.scalar_type() == q.scalar_type() &&
+                  dv.scalar_type() == q.scalar_type(),
+              "flash_attn_bwd: dq / dk / dv must have the sizes and dtype of q / k / v");
+  // grouped-query attention: the kernels write dK / dV per QUERY head into contiguous [B, Sk, H, D]
+  // scratch; attn_kv_group_reduce then sums each group of H / Hk heads into the caller's dk / dv
+  const bool grouped = a.kv_group > 1;
+  Tensor dk_x, dv_x;
+  if (grouped) {
+    TORCH_CHECK(!(dsum.has_value() && dsum->defined()),
+                "flash_attn_bwd: dsum (the packed-QKV bias gradient) is not supported with grouped K/V heads");
+    TORCH_CHECK(!(q8_dq.has_value() && q8_dq->defined()) && !(q8_dk.has_value() && q8_dk->defined()) &&
+                    !(q8_dv.has_value() && q8_dv->defined()) && !q8_only,
+                "flash_attn_bwd: the fp8 code outputs (q8_dq / q8_dk / q8_dv / q8_only) are not supported "
+                "with grouped K/V heads");
+    dk_x = at::empty({a.B, a.Sk, a.H, a.D}, q.options());
+    dv_x = at::empty({a.B, a.Sk, a.H, a.D}, q.options());
+    attn_set(a, dk_x, a.dk_bs, a.dk_ss, a.dk_hs);
+    attn_set(a, dv_x, a.dv_bs, a.dv_ss, a.dv_hs);
+  }
   a.dq = dq.data_ptr();
   a.mask_words = 2 * (((int64_t)a.Sk + 31) / 32);
   if (a.drop_thresh) {
@@ -488,8 +538,10 @@ bool flash_attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor 
     q8 = true;
   }
   check(apex::attn_bwd(a, dout.data_ptr(), delta_ws.defined() ? delta_ws.data_ptr<float>() : nullptr,
-                       dk.data_ptr(), dv.data_ptr(), dt_code(q.scalar_type()), cur_stream()),
+                       grouped ? dk_x.data_ptr() : dk.data_ptr(), grouped ? dv_x.data_ptr() : dv.data_ptr(),
+                       dt_code(q.scalar_type()), cur_stream()),
         "attn_bwd");
+  if (grouped) attn_kv_group_reduce(dk_x, dv_x, dk, dv);
   return q8;
 }
 
@@ -1618,6 +1670,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q8_dq") = py::none(), py::arg("q8_dk") = py::none(), py::arg("q8_dv") = py::none(),
         py::arg("q8_scale") = py::none(), py::arg("q8_amax") = py::none(), py::arg("q8_fmt") = 0,
         py::arg("dbias") = py::none(), py::arg("q8_only") = false);
+  m.def("attn_kv_group_reduce", &attn_kv_group_reduce, py::arg("dk_x"), py::arg("dv_x"), py::arg("dk"), py::arg("dv"));
   m.def("partial_colsum", &k_partial_colsum, py::arg("part"), py::arg("out_dtype"), py::arg("out") = py::none());
   m.def("flash_dropout_mask", &flash_dropout_mask);
   m.def("lse_merge", &k_lse_merge, py::arg("acc_o"), py::arg("acc_lse"), py::arg("o"), py::arg("lse"),

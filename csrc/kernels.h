@@ -122,6 +122,11 @@ struct AttnArgs {
   // backward with q8dq..: dq / dk / dv are NOT stored, only their codes (their consumers, the QKV
   // input-gradient GEMM and weight gradient, read codes alone: apex.fp8 codes_only_ok)
   int q8only;
+  // grouped-query attention: kv_group = H / Hk consecutive query heads share one K/V head, so k / v
+  // are [B, Sk, H / kv_group, D] and query head h reads K/V head h / kv_group. 0 or 1: one K/V head
+  // per query head (MHA). Everything else, dk / dv included, stays indexed by the query head: the
+  // backward writes per-query-head dk / dv ([B, Sk, H, D]) and attn_kv_group_reduce sums each group.
+  int kv_group;
 };
 inline uint32_t attn_drop_thresh(double p) {  // 8-bit keep threshold in [1, 255], 0 = off
   if (p <= 0.0) return 0u;
@@ -134,6 +139,13 @@ bool attn_bwd_split();
 // delta_ws: [B*H*Sq] fp32 workspace when attn_bwd_needs_dq_acc (two-kernel backward)
 int attn_bwd(const AttnArgs& a, const void* dout, float* delta_ws, void* dk, void* dv, int dt,
              hipStream_t s);
+// grouped-query backward: dk[b, s, j, :] = sum over i < g of dk_x[b, s, j * g + i, :] (and the same
+// for dv), one launch for both. dk_x / dv_x are contiguous [B, Sk, Hk * g, D]; dk / dv are
+// [B, Sk, Hk, D] views with element strides (D contiguous, 16-byte aligned). fp32 accumulation in
+// ascending head order, one rounding. D * sizeof(dtype) % 16 == 0.
+int attn_kv_group_reduce(const void* dk_x, const void* dv_x, void* dk, void* dv, int64_t B, int64_t Sk,
+                         int Hk, int g, int D, int64_t dk_bs, int64_t dk_ss, int64_t dk_hs, int64_t dv_bs,
+                         int64_t dv_ss, int64_t dv_hs, int dt, hipStream_t s);
 // context parallelism: acc (fp32 [B,S,H,D] + lse [B,H,S]) <- exact log-sum-exp merge with one block's
 // (o [B,S,H,D] in dt, lse [B,H,S]); first = 1 initialises the accumulator from the block
 int lse_merge(float* acc_o, float* acc_lse, const void* o, const float* lse, int64_t B, int S, int H, int D,
