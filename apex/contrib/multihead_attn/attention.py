@@ -7,7 +7,7 @@ takes k / v with hk < h heads (h % hk == 0), and ``attention_grouped_packed(qkv[
 kernels read each K/V head once per query head of its group, nothing is expanded.
 
 Every bf16/fp16 device call runs the MFMA flash-attention kernels in apex._C
-(csrc/attention_impl.h):
+(csrc/attention_fwd.h, csrc/attention_bwd.h; launchers in csrc/attention_impl.h):
 
 * head dims 32 / 64 / 128 / 256 natively; any other head dim up to 256 (multiple of 8) is
   zero-padded to the next of those (zero columns add nothing to Q K^T, and the padded V columns

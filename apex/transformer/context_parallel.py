@@ -3,7 +3,7 @@
 The reference has no sequence-length parallelism at all (its only sequence mechanism is
 the word LM's truncated BPTT, /root/reference/examples/word_language_model/main.py:119-124). This
 module adds the two standard long-context schemes on top of the flash-attention kernels
-(csrc/attention_impl.h) and torch.distributed (RCCL over xGMI on MI355X, gloo on CPU):
+(csrc/attention_fwd.h, csrc/attention_bwd.h) and torch.distributed (RCCL over xGMI on MI355X, gloo on CPU):
 
 * ``ring_attention``: every rank keeps its query shard; the K/V shards travel around the CP ring
   (one P2P exchange per step, issued before that step's block attention so the transfer overlaps

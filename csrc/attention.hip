@@ -1,7 +1,7 @@
 // Flash attention (NS-05): head-dim dispatch and the dropout-mask debug kernel. The kernel
-// templates live in attention_impl.h; attention_d{32,64,128,256}.hip instantiate one head dim
-// each so the (many) variants compile in parallel.
-#include "attention_impl.h"
+// templates live in attention_fwd.h / attention_bwd.h; attention_d{32,64,128,256}.hip instantiate
+// one head dim each (launchers: attention_impl.h) so the (many) variants compile in parallel.
+#include "attention_impl.h"  // entry points; drop_block_bits and kBwdBK come from attention_common.h
 
 namespace apex {
 
@@ -44,15 +44,8 @@ int attn_fwd(const AttnArgs& a, int dt, hipStream_t s) {
 }
 
 // Two-kernel backward (key-stationary dK/dV + query-stationary dQ, delta pre-pass) for key ranges
-// longer than one 128-key block; APEX_ATTN_BWD_SPLIT=1 also selects it for short ones (A/B knob)
-bool attn_bwd_split() {
-  static const bool on = [] {
-    const char* e = getenv("APEX_ATTN_BWD_SPLIT");
-    return e && e[0] == '1';
-  }();
-  return on;
-}
-bool attn_bwd_needs_dq_acc(const AttnArgs& a) { return a.Sk > kBwdBK || attn_bwd_split(); }
+// longer than one 128-key block
+bool attn_bwd_needs_dq_acc(const AttnArgs& a) { return a.Sk > kBwdBK; }
 
 int attn_bwd(const AttnArgs& a, const void* dout, float* delta_ws, void* dk, void* dv, int dt,
              hipStream_t s) {

@@ -1,4 +1,4 @@
-// Flash attention kernels instantiated for head dim 256 (templates: attention_impl.h).
+// Flash attention kernels instantiated for head dim 256 (launchers: attention_impl.h; kernels: attention_fwd.h, attention_bwd.h).
 #include "attention_impl.h"
 
 namespace apex {

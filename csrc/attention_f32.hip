@@ -2,10 +2,10 @@
 // accumulate, bit-for-bit an fmaf chain; 1/16 of the bf16 matrix rate, the same as the f32 VALU
 // peak but one VGPR per operand and the VALU left free for the softmax).
 //
-// Rounds 1-3 ran fp32 attention as torch compositions (the dense matmul -> softmax -> dropout ->
-// matmul reference at training lengths, a query-blocked recomputation beyond): every [B, h, S, S]
-// intermediate makes a round trip through HBM, ~3 elementwise passes each way. Here the scores
-// never leave registers (same semantics as the bf16 kernels in attention_impl.h: causal mask
+// The alternative, fp32 attention as torch compositions (the dense matmul -> softmax -> dropout ->
+// matmul reference at training lengths, a query-blocked recomputation beyond), sends every
+// [B, h, S, S] intermediate through HBM, ~3 elementwise passes each way. Here the scores never
+// leave registers (same semantics as the 16-bit kernels in attention_fwd.h / attention_bwd.h: causal mask
 // key > query, per-batch key lengths, an additive [B|1, H|1, Sq|1, Sk] score bias, Philox-seeded
 // dropout with the keep bits stored for backward; fp32 log-sum-exp, natural log, +inf for a row
 // with no visible key). Head dims 32 / 64 / 128 (the Python side pads others up to 128).
@@ -15,7 +15,7 @@
 // (r & 3) + 8 (r >> 2) + 4 (l >> 5) in registers r = 0..15):
 //  * forward (per wave 32 queries): S^T = K . Q^T with the contraction permuted so MFMA s takes
 //    d = s + (l >> 5) D / 2 — every lane reads its operand as float4 runs — leaving lane
-//    (query, half) with 16 keys kappa(i, half) = (i & 3) + 8 (i >> 2) + 4 half of its query; the
+//    (query, half) with 16 keys kappa(i, half) (attention_common.h) of its query; the
 //    next product O^T = V^T . P^T sums over exactly that row index, so P^T is the B operand as it
 //    stands (no transpose, no LDS round trip) and V^T is staged transposed [D][32 + 4];
 //  * dK/dV (key-stationary, per wave 32 keys): S = Q . K^T and dP = dO . V^T leave lane
@@ -25,9 +25,8 @@
 //    dQ^T = K^T . dS^T (K^T staged transposed): each workgroup owns its dQ rows, no atomics.
 // The softmax scale is folded into Q once (the forward's and the dQ kernel's Q registers, the
 // dK/dV kernel's staged Q tile — which makes dK = dS^T (scale Q) with no epilogue multiply).
-// Reference: apex/contrib/csrc/multihead_attn (fp32 softmax inside the fused MHA kernels) —
-// /root/reference/apex/contrib/csrc/multihead_attn/softmax.cuh.
-#include "attention_impl.h"
+// Reference: apex/contrib/csrc/multihead_attn (fp32 softmax inside the fused MHA kernels).
+#include "attention_bwd.h"  // attn_bwd_delta_kernel; the shared primitives come with it
 
 namespace apex {
 namespace {
@@ -143,8 +142,6 @@ __device__ __forceinline__ void store_rows(float* p, int hl, const f32x16 (&acc)
           make_float4(acc[db][4 * g] * mul, acc[db][4 * g + 1] * mul, acc[db][4 * g + 2] * mul, acc[db][4 * g + 3] * mul);
 }
 
-__device__ __forceinline__ int kappa(int i, int hl) { return (i & 3) + 8 * (i >> 2) + 4 * hl; }
-
 // ---------------------------------------------------------------------------------------------
 // forward: grid (B*H, query blocks of 128), heaviest (causal: last) blocks first; 4 waves x 32 queries
 // ---------------------------------------------------------------------------------------------
@@ -232,7 +229,7 @@ __global__ void __launch_bounds__(256) attn_f32_fwd_kernel(AttnArgs a) {
       const float p = __builtin_amdgcn_exp2f(fmaf(st[i], kLog2e, ms));
       psum += p;
       st[i] = DROPOUT ? __builtin_bit_cast(float, __builtin_bit_cast(int, p) &
-                                                      __builtin_amdgcn_sbfe((int)mcur, (i & 3) + 8 * (i >> 2), 1))
+                                                      __builtin_amdgcn_sbfe((int)mcur, kappa(i), 1))
                       : p;
     }
     l = l * alpha + psum;
@@ -344,7 +341,7 @@ __global__ void __launch_bounds__(256) attn_f32_bwd_dkdv_kernel(AttnArgs a, cons
         ds[i] = pv * (dpv - del[e]);
       }
     }
-    if (BIAS && a.dbias) {  // trainable bias: its gradient is dS (see attention_impl.h)
+    if (BIAS && a.dbias) {  // trainable bias: its gradient is dS (see attention_bwd.h)
       float* dcol = a.dbias + b * a.dbias_bs + h * a.dbias_hs + key;
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
@@ -433,6 +430,8 @@ __global__ void __launch_bounds__(256) attn_f32_bwd_dq_kernel(AttnArgs a, const 
         float pv = __builtin_amdgcn_exp2f((s[i] + bv[e] - lse) * kLog2e);
         if (kb + kappa(i, hl) >= lim) pv = 0.f;
         float dpv = dp[i];
+        // bit kappa(i) of the shifted word; written out, because the call changes this kernel's
+        // register assignment (profiles/README.md, "Attention unit split")
         if (DROPOUT) dpv = (mcur >> ((i & 3) + 8 * (i >> 2))) & 1u ? dpv * a.drop_scale : 0.f;
         ds[i] = pv * (dpv - del);
       }
@@ -442,14 +441,10 @@ __global__ void __launch_bounds__(256) attn_f32_bwd_dq_kernel(AttnArgs a, const 
   if (qok) store_rows<D>((float*)a.dq + b * a.dq_bs + h * a.dq_hs + (int64_t)qrow * a.dq_ss, hl, dqt, a.scale);
 }
 
-#define F32_DISPATCH_B(X, NAME, ...)                  \
-  if (X) { constexpr bool NAME = true; __VA_ARGS__; } \
-  else { constexpr bool NAME = false; __VA_ARGS__; }
-
 template <int D>
 int fwd_d(const AttnArgs& a, hipStream_t s) {
   const dim3 grid(a.B * a.H, (a.Sq + kF32Rows - 1) / kF32Rows);
-  F32_DISPATCH_B(a.causal, C, F32_DISPATCH_B(a.drop_thresh > 0, DR, F32_DISPATCH_B(a.bias != nullptr, BI, {
+  APEX_DISPATCH_B(a.causal, C, APEX_DISPATCH_B(a.drop_thresh > 0, DR, APEX_DISPATCH_B(a.bias != nullptr, BI, {
     hipLaunchKernelGGL((attn_f32_fwd_kernel<D, C, DR, BI>), grid, dim3(256), 0, s, a);
   })));
   return (int)hipGetLastError();
@@ -461,7 +456,7 @@ int bwd_d(const AttnArgs& a, const float* dout, float* delta, float* dk, float* 
   hipLaunchKernelGGL((attn_bwd_delta_kernel<float, D>), dgrid, dim3(256), 0, s, a, (const void*)dout, delta);
   const dim3 kgrid(a.B * a.H, (a.Sk + kF32Rows - 1) / kF32Rows);
   const dim3 qgrid(a.B * a.H, (a.Sq + kF32Rows - 1) / kF32Rows);
-  F32_DISPATCH_B(a.causal, C, F32_DISPATCH_B(a.drop_thresh > 0, DR, F32_DISPATCH_B(a.bias != nullptr, BI, {
+  APEX_DISPATCH_B(a.causal, C, APEX_DISPATCH_B(a.drop_thresh > 0, DR, APEX_DISPATCH_B(a.bias != nullptr, BI, {
     hipLaunchKernelGGL((attn_f32_bwd_dkdv_kernel<D, C, DR, BI>), kgrid, dim3(256), 0, s, a, dout,
                        (const float*)delta, dk, dv);
     hipLaunchKernelGGL((attn_f32_bwd_dq_kernel<D, C, DR, BI>), qgrid, dim3(256), 0, s, a, dout,

@@ -528,7 +528,7 @@ bool flash_attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor 
   const bool two_kernel = q.scalar_type() == at::kFloat || apex::attn_bwd_needs_dq_acc(a);
   if (two_kernel) delta_ws = at::empty({rows}, q.options().dtype(at::kFloat));
   bool q8 = false;
-  if (!two_kernel && !apex::attn_bwd_split() && q8_dq.has_value() && q8_dq->defined()) {
+  if (!two_kernel && q8_dq.has_value() && q8_dq->defined()) {
     a.q8dq = attn_q8(q8_dq, dq, "flash_attn_bwd dq");
     a.q8dk = attn_q8(q8_dk, dk, "flash_attn_bwd dk");
     a.q8dv = attn_q8(q8_dv, dv, "flash_attn_bwd dv");

@@ -230,7 +230,8 @@ __device__ __forceinline__ float u32_to_unit(uint32_t x) {
 }  // namespace apex
 
 // Host-side launchers: run the statement with T bound to the element type of dtype code DT
-// (16-bit-only attention has its own ATTN_DISPATCH), or with a constexpr bool NAME bound to X.
+// (16-bit-only attention has its own ATTN_DISPATCH in attention_impl.h), or with a constexpr bool
+// NAME bound to X.
 #define APEX_DISPATCH_T(DT, T, ...)                         \
   switch (DT) {                                             \
     case kF32: { using T = float; __VA_ARGS__; } break;     \

@@ -1,6 +1,6 @@
 """Kernel-by-kernel equality of two hipcc -S (--cuda-device-only) gfx950 assembly files.
 
-  python tools/isa_diff.py <a.s> <b.s> [--list]
+  python tools/isa_diff.py <a.s> <b.s> [--list] [--rename-a OLD NEW]
 
 Splits both files by kernel symbol (every .amdhsa_kernel name). A kernel's text is its
 instructions (from its label to .Lfunc_end) plus its .amdhsa_kernel descriptor (registers,
@@ -13,13 +13,20 @@ function that is not inlined would be a symbol of its own outside every kernel: 
 (.type <sym>,@function without a descriptor) are counted and, if there are any, fail the run.
 Prints the number of kernels compared, the symbols present on one side only and the symbols
 that differ; exit status 1 unless all three are empty. It looks at nothing but equality.
+--rename-a OLD NEW: for a change that renames kernels (a template parameter dropped: the argument
+list is part of the mangled name), re.sub(OLD, NEW) is applied to the text of <a.s> before
+anything else, so to the symbol names and to wherever they stand in the compared text; OLD should
+be written to match inside those symbol names only. The rule is printed with the result.
 """
 import re
 import sys
 
 
-def kernels(path):
-    lines = open(path).read().split("\n")
+def kernels(path, rename=None):
+    text = open(path).read()
+    if rename:
+        text = re.sub(rename[0], rename[1], text)
+    lines = text.split("\n")
     names = [l.split()[1] for l in lines if l.strip().startswith(".amdhsa_kernel ")]
     want = set(names)
     funcs = [m.group(1) for m in (re.match(r"\s*\.type\s+([^,\s]+),@function", l) for l in lines) if m]
@@ -48,7 +55,12 @@ def kernels(path):
 
 
 def main():
-    (a, oa), (b, ob) = kernels(sys.argv[1]), kernels(sys.argv[2])
+    rename = None
+    if "--rename-a" in sys.argv:
+        i = sys.argv.index("--rename-a")
+        rename = (sys.argv[i + 1], sys.argv[i + 2])
+        print(f"rename rule for {sys.argv[1]}: {rename[0]} -> {rename[1]}")
+    (a, oa), (b, ob) = kernels(sys.argv[1], rename), kernels(sys.argv[2])
     only_a = sorted(set(a) - set(b))
     only_b = sorted(set(b) - set(a))
     both = sorted(set(a) & set(b))
