@@ -2,8 +2,9 @@
 
 ``FusedScaleMaskSoftmax(input_in_fp16, input_in_bf16, attn_mask_type, scaled_masked_softmax_fusion,
 mask_func, softmax_in_fp32, scale)``; ``forward(input[b, np, sq, sk], mask[b, 1, sq, sk])``.
-Fused path: fp16/bf16 input, sk % 8 == 0 and sk <= 4096 (one wave64 per row in registers);
-otherwise the PyTorch formulation (mask_func + softmax in fp32).
+Fused path: fp16/bf16 input, sk % 8 == 0 and sk <= 4096 (one wave64 per row in registers),
+16-byte aligned rows and a mask of exactly [b, 1|np, sq, sk]; otherwise (a mask broadcast over the
+batch or the queries, a misaligned view) the PyTorch formulation (mask_func + softmax in fp32).
 """
 from __future__ import annotations
 
@@ -24,7 +25,7 @@ class ScaledUpperTriangMaskedSoftmax(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         (y,) = ctx.saved_tensors
-        return _ext.require().scaled_masked_softmax_bwd(dy, y, float(ctx.scale)), None
+        return _ext.require().scaled_masked_softmax_bwd(_packed(dy), y, float(ctx.scale)), None
 
 
 class ScaledMaskedSoftmax(torch.autograd.Function):
@@ -40,7 +41,7 @@ class ScaledMaskedSoftmax(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         (y,) = ctx.saved_tensors
-        return _ext.require().scaled_masked_softmax_bwd(dy, y, float(ctx.scale)), None, None
+        return _ext.require().scaled_masked_softmax_bwd(_packed(dy), y, float(ctx.scale)), None, None
 
 
 class ScaledSoftmax(torch.autograd.Function):
@@ -54,7 +55,7 @@ class ScaledSoftmax(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         (y,) = ctx.saved_tensors
-        return _ext.require().scaled_masked_softmax_bwd(dy, y, float(ctx.scale)), None
+        return _ext.require().scaled_masked_softmax_bwd(_packed(dy), y, float(ctx.scale)), None
 
 
 class FusedScaleMaskSoftmax(torch.nn.Module):
@@ -76,18 +77,32 @@ class FusedScaleMaskSoftmax(torch.nn.Module):
 
     def forward(self, input, mask):
         assert input.dim() == 4
-        if input.is_cuda and self.is_kernel_available(mask, *input.size()):
+        if input.is_cuda and self.is_kernel_available(mask, *input.size(), input=input):
             return self.forward_fused_softmax(input, mask)
         return self.forward_torch_softmax(input, mask)
 
-    def is_kernel_available(self, mask, b, np, sq, sk):
+    def is_kernel_available(self, mask, b, np, sq, sk, input=None):
+        """True when the fused kernels take this call; everything else goes to
+        ``forward_torch_softmax``. The kernels want 16-byte aligned rows and, in padding mode, a mask
+        of exactly ``[b, 1|np, sq, sk]``: a broadcast batch (``[1, 1, sq, sk]`` with ``b > 1``) or a
+        broadcast query dimension (``[b, 1, 1, sk]``) is left to ``mask_func``."""
         if not (self.scaled_masked_softmax_fusion and self.input_in_float16 and input_is_native()):
             return False
         C = _ext.require()
         if not C.scaled_softmax_supported(sk):
             return False
+        # a non-contiguous input is copied (and so aligned) on the way in
+        if input is not None and input.is_contiguous() and not _aligned16(input):
+            return False
         if self.attn_mask_type == AttnMaskType.causal:
             return sq == sk
+        if mask is not None:
+            if mask.dim() != 4 or mask.shape[0] != b or mask.shape[1] not in (1, np) \
+                    or tuple(mask.shape[2:]) != (sq, sk):
+                return False
+            # a uint8 mask is handed over as it is, any other dtype is copied first
+            if mask.dtype == torch.uint8 and mask.is_contiguous() and not _aligned16(mask):
+                return False
         return True
 
     def forward_fused_softmax(self, input, mask):
@@ -115,6 +130,16 @@ class FusedScaleMaskSoftmax(torch.nn.Module):
     @staticmethod
     def get_batch_per_block(sq, sk, b, np):
         return 4  # one wave64 per row, 4 rows per 256-thread block
+
+
+def _aligned16(t):
+    return t.data_ptr() % 16 == 0
+
+
+def _packed(dy):
+    """dy contiguous and 16-byte aligned (a copy when it is a misaligned view)."""
+    dy = dy.contiguous()
+    return dy if _aligned16(dy) else dy.clone()
 
 
 _native_flag = [None]

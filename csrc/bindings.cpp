@@ -259,8 +259,10 @@ std::vector<Tensor> ln_bwd(Tensor dy, Tensor x, int64_t cols, const c10::optiona
   const bool hb = beta.has_value() && beta->defined();
   Tensor dgamma = hg ? out_or_empty(dgamma_out, gamma->sizes(), gamma->options(), "layer_norm_bwd dgamma") : Tensor();
   Tensor dbeta = hb ? out_or_empty(dbeta_out, beta->sizes(), beta->options(), "layer_norm_bwd dbeta") : Tensor();
+  TORCH_CHECK(hg || !hb, "layer_norm_bwd: beta without gamma is not supported");
+  // the fast and wide kernels store their per-block partials whether or not anyone sums them
   Tensor ws;
-  if (hg || hb)
+  if (rows > 0)
     ws = at::empty({apex::layer_norm_bwd_ws_floats(rows, (int)cols)}, x.options().dtype(at::kFloat));
   const int wdt = hg ? dt_code(gamma->scalar_type()) : dt_code(x.scalar_type());
   check(apex::layer_norm_bwd(dy.data_ptr(), x.data_ptr(), opt_vptr(gamma),
@@ -1066,16 +1068,28 @@ std::vector<Tensor> k_bn_bwd_elemt(Tensor dy, Tensor x, Tensor mean, Tensor invs
 // --------------------------------------------------------------------------
 bool k_smx_supported(int64_t cols) { return apex::scaled_softmax_supported((int)cols) != 0; }
 
+static inline bool smx_aligned(const Tensor& t) { return ((uintptr_t)t.data_ptr() & 15) == 0; }
+
 Tensor k_smx_fwd(Tensor x, const c10::optional<Tensor>& mask, double scale, int64_t mode, int64_t heads) {
   TORCH_CHECK(x.is_contiguous() && x.dim() >= 2, "scaled_masked_softmax: contiguous input");
+  TORCH_CHECK(mode >= 0 && mode <= 2, "scaled_masked_softmax: mode must be 0 (none), 1 (mask) or 2 (causal)");
   const int64_t cols = x.size(-1), sq = x.size(-2);
-  const int64_t rows = x.numel() / cols;
+  const int64_t rows = cols ? x.numel() / cols : 0;
   Tensor y = at::empty_like(x);
+  // the kernels move 16-byte packs (rows are cols % 8 == 0 elements apart)
+  TORCH_CHECK(rows == 0 || (smx_aligned(x) && smx_aligned(y)), "scaled_masked_softmax: x / y must be 16-byte aligned");
   const uint8_t* mp = nullptr;
   int mask_heads = 1;
   if (mode == 1) {
     TORCH_CHECK(mask.has_value() && mask->defined() && mask->is_contiguous(), "mask required");
+    TORCH_CHECK(mask->scalar_type() == at::kByte || mask->scalar_type() == at::kBool,
+                "scaled_masked_softmax: mask must be uint8 or bool");
+    TORCH_CHECK(x.dim() == 4 && x.size(1) == heads, "scaled_masked_softmax: masked input must be [B, heads, sq, sk]");
+    TORCH_CHECK(mask->dim() == 4, "scaled_masked_softmax: mask must be 4-D [B, 1|heads, sq, sk]");
     TORCH_CHECK(mask->size(-1) == cols && mask->size(-2) == sq, "mask shape mismatch");
+    TORCH_CHECK(mask->size(0) == x.size(0), "scaled_masked_softmax: mask batch must equal the input batch");
+    TORCH_CHECK(mask->size(1) == 1 || mask->size(1) == heads, "scaled_masked_softmax: mask heads must be 1 or heads");
+    TORCH_CHECK(smx_aligned(*mask), "scaled_masked_softmax: mask must be 16-byte aligned");
     mp = (const uint8_t*)mask->data_ptr();
     mask_heads = (int)mask->size(1);
   }
@@ -1087,9 +1101,13 @@ Tensor k_smx_fwd(Tensor x, const c10::optional<Tensor>& mask, double scale, int6
 }
 
 Tensor k_smx_bwd(Tensor dy, Tensor y, double scale) {
+  TORCH_CHECK(y.is_contiguous() && y.dim() >= 2, "scaled_masked_softmax_bwd: contiguous y");
+  TORCH_CHECK(dy.sizes() == y.sizes() && dy.scalar_type() == y.scalar_type(), "scaled_masked_softmax_bwd: dy like y");
   Tensor dyc = dy.contiguous();
-  const int64_t cols = y.size(-1), rows = y.numel() / cols;
+  const int64_t cols = y.size(-1), rows = cols ? y.numel() / cols : 0;
   Tensor dx = at::empty_like(y);
+  TORCH_CHECK(rows == 0 || (smx_aligned(dyc) && smx_aligned(y) && smx_aligned(dx)),
+              "scaled_masked_softmax_bwd: dy / y / dx must be 16-byte aligned");
   check(apex::scaled_masked_softmax_bwd(dyc.data_ptr(), y.data_ptr(), dx.data_ptr(), rows, (int)cols,
                                         (float)scale, dt_code(y.scalar_type()), cur_stream()),
         "scaled_masked_softmax_bwd");

@@ -13,10 +13,31 @@ namespace apex {
 
 constexpr int kXeBlock = 256;
 
+// (m, s) <- merge with (m2, s2): s = s e^(m - mn) + s2 e^(m2 - mn), mn = max(m, m2).
+// How that sum is rounded is spelled out. Left to the compiler, which product goes into the fused
+// multiply-add, or neither once both are packed into one multiply, changes with the surrounding
+// code: every edit of this file could move the last bit of lse, and with it every gradient of a
+// training run. FUSED: fma(s2, e2, round(s e1)); otherwise both products are rounded. Each call site
+// keeps the form it has always had.
+__device__ __forceinline__ float sum2_rounded(float a, float b, float c, float d) {
+#pragma clang fp contract(off)
+  return a * b + c * d;
+}
+
+template <bool FUSED>
 __device__ __forceinline__ void online_merge(float& m, float& s, float m2, float s2) {
   const float mn = fmaxf(m, m2);
   if (mn == -INFINITY) return;
-  s = s * __expf(m - mn) + s2 * __expf(m2 - mn);
+  const float e1 = __expf(m - mn), e2 = __expf(m2 - mn);
+  s = FUSED ? fmaf(s2, e2, s * e1) : sum2_rounded(s, e1, s2, e2);
+  m = mn;
+}
+
+// merge with one element v: s = fma(s, e^(m - mn), e^(v - mn))
+__device__ __forceinline__ void online_add(float& m, float& s, float v) {
+  const float mn = fmaxf(m, v);
+  if (mn == -INFINITY) return;
+  s = fmaf(s, __expf(m - mn), __expf(v - mn));
   m = mn;
 }
 
@@ -38,18 +59,20 @@ __global__ void __launch_bounds__(kXeBlock) xent_fwd_kernel(const T* __restrict_
       float lm = v[0];
 #pragma unroll
       for (int k = 1; k < 8; ++k) lm = fmaxf(lm, v[k]);
+      // a group that is all -inf (a masked vocabulary pad): subtract 0, so that ls is 0 and not NaN
+      const float sub = lm == -INFINITY ? 0.f : lm;
       float ls = 0.f;
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        ls += __expf(v[k] - lm);
+        ls += __expf(v[k] - sub);
         sumx += v[k];
       }
-      online_merge(m, s, lm, ls);
+      online_merge<false>(m, s, lm, ls);
     }
   } else {
     for (int i = threadIdx.x; i < V; i += kXeBlock) {
       const float v = to_f(xr[i]);
-      online_merge(m, s, v, 1.f);
+      online_add(m, s, v);
       sumx += v;
     }
   }
@@ -57,7 +80,10 @@ __global__ void __launch_bounds__(kXeBlock) xent_fwd_kernel(const T* __restrict_
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    online_merge(m, s, m2, s2);
+    // the last step and the 16-byte loop above have always rounded both products (compiled as one
+    // packed multiply), the other merges fuse one: kept, so that lse stays bit for bit what it was
+    if (o > 1) online_merge<true>(m, s, m2, s2);
+    else online_merge<false>(m, s, m2, s2);
     sumx += __shfl_xor(sumx, o, 64);
   }
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -70,7 +96,7 @@ __global__ void __launch_bounds__(kXeBlock) xent_fwd_kernel(const T* __restrict_
   if (threadIdx.x == 0) {
     float M = sm[0], S = ss[0], X = sx[0];
     for (int w = 1; w < kXeBlock / 64; ++w) {
-      online_merge(M, S, sm[w], ss[w]);
+      online_merge<true>(M, S, sm[w], ss[w]);
       X += sx[w];
     }
     const float lse = M + __logf(S);
@@ -80,7 +106,13 @@ __global__ void __launch_bounds__(kXeBlock) xent_fwd_kernel(const T* __restrict_
       loss[row] = 0.f;
     } else {
       const float xy = to_f(xr[y]);
-      loss[row] = (1.f - smoothing) * (lse - xy) + smoothing * (lse - X / (float)V);
+      // lse - x_y and lse - mean(x) as (M - .) + log S: the differences are taken before log S is
+      // added, so logits moved by a constant give the same loss (lse itself rounds at |M|).
+      // Without smoothing sum(x) stays out: it is -inf for a row with masked columns
+      const float lS = __logf(S);
+      float l = (1.f - smoothing) * ((M - xy) + lS);
+      if (smoothing != 0.f) l += smoothing * ((M - X / (float)V) + lS);
+      loss[row] = l;
     }
   }
 }
