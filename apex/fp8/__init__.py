@@ -500,7 +500,10 @@ class Fp8State:
         if not s or not C.gemm_tt_f8_supported(d8, x8, s):
             return None
         self.wgrad_calls += 1
-        return C.gemm_tt_f8(d8, x8, sd, sx, self._bwd, self._fwd, s, out_dtype, out=out)
+        # (splitk_reduce stores 16-byte vectors: a slot it cannot take is filled by a copy of the result)
+        ok = out is None or (out.is_contiguous() and out.device == d8.device and out.data_ptr() % 16 == 0)
+        r = C.gemm_tt_f8(d8, x8, sd, sx, self._bwd, self._fwd, s, out_dtype, out=out if ok else None)
+        return r if ok else out.copy_(r.view(out.shape))
 
     # ------------------------------------------------------------------ step
     def step(self):

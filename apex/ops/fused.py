@@ -203,7 +203,10 @@ def accumulate_main_grad(mg, dy2, x2):
         torch.addmm(mg, dy2.t(), x2, out_dtype=torch.float32, out=mg)
         return mg
     slabs = torch.bmm(dy2.view(s, M // s, N).transpose(1, 2), x2.view(s, M // s, K), out_dtype=torch.float32)
-    _ext.require().splitk_reduce(slabs, torch.float32, mg, accumulate=True)
+    if mg.data_ptr() % 16 == 0 and mg.device == dy2.device:
+        _ext.require().splitk_reduce(slabs, torch.float32, mg, accumulate=True)
+    else:  # (splitk_reduce stores 16-byte vectors: an unaligned main_grad takes the sum through a temporary)
+        mg.add_(_ext.require().splitk_reduce(slabs, torch.float32))
     return mg
 
 
@@ -232,10 +235,19 @@ def _wgrad(dy2, x2, out=None, param=None, f8=None):
             return main_grad_placeholder(param)
         if out is None:
             out = _gt(param)
-    if f8 is not None and f8[0] is not None and (out is None or out.is_contiguous()):
-        r = f8[0].wgrad(f8[1], f8[2], dy2.dtype, out=out)
+    # the split-K reduction (splitk_reduce, behind every kernel path here) stores 16-byte vectors: a slot
+    # it cannot take (unaligned, e.g. APEX_DDP_ALIGN=0, not contiguous, another device) is filled by a
+    # copy of the kernels' own result
+    slot_ok = out is None or (out.is_contiguous() and out.device == dy2.device and out.data_ptr() % 16 == 0)
+    kout = out if slot_ok else None
+
+    def _filled(r):
+        return r if kout is out else out.copy_(r.view(out.shape))
+
+    if f8 is not None and f8[0] is not None:
+        r = f8[0].wgrad(f8[1], f8[2], dy2.dtype, out=kout)
         if r is not None:
-            return r
+            return _filled(r)
     M, N = dy2.shape
     K = x2.shape[1]
     s = _wgrad_splits(M, N, K) if dy2.dtype in (torch.bfloat16, torch.float16) else 1
@@ -246,14 +258,14 @@ def _wgrad(dy2, x2, out=None, param=None, f8=None):
         st = _wgrad_tt_splits(M, N, K)
         if G.mode() == "mfma" and not st:
             st = max(s, 4 if M >= 16384 else 1)
-        if st and C.gemm_tt_supported(dy2, x2, st) and (out is None or out.is_contiguous()):
+        if st and C.gemm_tt_supported(dy2, x2, st):
             # hand-written transposed-read MFMA GEMM (csrc/gemm.hip); the split-K reduction writes
             # the gradient-bucket slot directly when one is given
-            return C.gemm_tt(dy2, x2, st, dy2.dtype, out=out)
+            return _filled(C.gemm_tt(dy2, x2, st, dy2.dtype, out=kout))
     if s == 1 or not (dy2.is_contiguous() and x2.is_contiguous()):
         return torch.mm(dy2.t(), x2, out=out) if out is not None else torch.mm(dy2.t(), x2)
     slabs = torch.bmm(dy2.view(s, M // s, N).transpose(1, 2), x2.view(s, M // s, K), out_dtype=torch.float32)
-    return _ext.require().splitk_reduce(slabs, dy2.dtype, out)
+    return _filled(_ext.require().splitk_reduce(slabs, dy2.dtype, kout))
 
 
 # ---------------------------------------------------------------------------

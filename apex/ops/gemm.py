@@ -38,8 +38,10 @@ Policy (``APEX_GEMM``):
                   for the FFN shapes with 4 K-slices; slower for QKV) — A/B and coverage runs
   blas            library GEMM + separate HIP epilogue kernels everywhere
 Each function falls back to the library path when the operands do not fit the MFMA kernel
-(K % 64, N % 8, dtype, alignment). Numerics follow the unfused composition: the GEMM result is
-rounded to the activation dtype before the bias/activation.
+(K % 64, N % 8, dtype, alignment), and when a bias, residual, stored activation or bias-gradient
+slot is one the binding refuses: on another device, or (the inputs) not 16-byte aligned. Numerics
+follow the unfused composition: the GEMM result is rounded to the activation dtype before the
+bias/activation.
 
 FP8: every function takes ``f8`` (an apex.fp8.Fp8State, captured by the calling autograd
 Function's forward from ``fp8_state()``); when given and the shapes fit (contraction % 128), the
@@ -89,6 +91,23 @@ def _2d(x):
     return x.reshape(-1, x.shape[-1])
 
 
+def _fits(a, *ts):
+    """The MFMA kernel can read these epilogue operands (bias, residual, stored activation): on a's
+    device and 16-byte aligned, as C.gemm requires; otherwise the caller takes its library path."""
+    return all(t is None or (t.device == a.device and t.data_ptr() % 16 == 0) for t in ts)
+
+
+def _slot_ok(a, out, n, dtype):
+    """``bias_grad_out`` as C.gemm takes it: a contiguous [n] tensor of ``dtype`` on a's device."""
+    return out is None or (dtype is not None and out.device == a.device and out.is_contiguous() and out.numel() == n
+                           and out.dtype == dtype)
+
+
+def _here(a, t):
+    """t on a's device (the library paths take operands the MFMA kernel refused)."""
+    return t if t is None or t.device == a.device else t.to(a.device)
+
+
 def mode() -> str:
     return _MODE
 
@@ -124,11 +143,11 @@ def linear(x, w, b=None, f8=None):
         r = f8.forward_gemm(a, w, C.EPI_BIAS if b is not None else C.EPI_NONE, b)
         if r is not None:
             return r[0].view(*x.shape[:-1], w.shape[0])
-    if use_mfma(a, w, fused=False) and (b is None or b.dtype == x.dtype):
+    if use_mfma(a, w, fused=False) and (b is None or (b.dtype == x.dtype and b.is_contiguous() and _fits(a, b))):
         C = _C()
         y, _ = C.gemm(a, w, C.EPI_BIAS if b is not None else C.EPI_NONE, b)
     else:
-        y = torch.addmm(b, a, w.t()) if b is not None else torch.mm(a, w.t())
+        y = torch.addmm(_here(a, b), a, w.t()) if b is not None else torch.mm(a, w.t())
     return y.view(*x.shape[:-1], w.shape[0])
 
 
@@ -145,9 +164,10 @@ def linear_gelu(x, w, b, act=ACT_GELU, f8=None, q8=None):
         if f8 is not None and b is not None else None
     if r is not None:
         return r[0].view(shp), r[1].view(shp)
-    if use_mfma(a, w) and b is not None and b.dtype == x.dtype:
+    if use_mfma(a, w) and b is not None and b.dtype == x.dtype and b.is_contiguous() and _fits(a, b):
         y, h = C.gemm(a, w, C.EPI_BIAS_GELU_TANH if act == ACT_GELU_TANH else C.EPI_BIAS_GELU, b)
     else:
+        b = _here(a, b)
         h = torch.mm(a, w.t())
         y = C.bias_act_fwd(h, b, act)
         h = h + b if b is not None else h  # the pre-activation as the fused path stores it
@@ -167,9 +187,10 @@ def linear_gelu_d(x, w, b, act=ACT_GELU, f8=None, q8=None, codes_only=False):
                         codes_only=codes_only) if f8 is not None and b is not None else None
     if r is not None:
         return r[0].view(shp), r[1].view(shp)
-    if use_mfma(a, w) and b is not None and b.dtype == x.dtype:
+    if use_mfma(a, w) and b is not None and b.dtype == x.dtype and b.is_contiguous() and _fits(a, b):
         y, gd = C.gemm(a, w, C.EPI_BIAS_GELU_TANH_D if act == ACT_GELU_TANH else C.EPI_BIAS_GELU_D, b)
     else:
+        b = _here(a, b)
         h = torch.mm(a, w.t())
         y = C.bias_act_fwd(h, b, act)
         gd, _ = C.bias_act_bwd(torch.ones_like(h), h, b, act)  # gelu'(h + b)
@@ -187,12 +208,13 @@ def dgrad_mul(dy, w, gd, bias_dtype, wT=None, f8=None, bias_grad_out=None, q8=No
     r = f8.backward_gemm(a, w, C.EPI_MUL, g2, bias_dtype, q8=q8, codes_only=codes_only) if f8 is not None else None
     if r is not None:
         return r
-    if _MODE != "blas" and a.is_cuda and g2.is_contiguous() and g2.dtype == a.dtype:
+    if (_MODE != "blas" and a.is_cuda and g2.is_contiguous() and g2.dtype == a.dtype and _fits(a, g2)
+            and _slot_ok(a, bias_grad_out, w.shape[1], bias_dtype)):
         wT = transpose(w) if wT is None else wT
         if use_mfma(a, wT):
             dh, db = C.gemm(a, wT, C.EPI_MUL, None, g2, bias_dtype, bias_grad_out)
             return dh, db
-    dh = torch.mm(a, w) * g2
+    dh = torch.mm(a, w) * _here(a, g2)
     db = C.colsum(dh, bias_dtype) if bias_dtype is not None else None
     return dh, db
 
@@ -222,13 +244,13 @@ def dgrad_resid(dy, w, r, wT=None, f8=None):
         res = f8.backward_gemm(a, w, _C().EPI_RESID, r2)
         if res is not None:
             return res[0].view(*dy.shape[:-1], w.shape[1])
-    if _MODE != "blas" and a.is_cuda and r2.is_contiguous() and r2.dtype == a.dtype:
+    if _MODE != "blas" and a.is_cuda and r2.is_contiguous() and r2.dtype == a.dtype and _fits(a, r2):
         wT = transpose(w) if wT is None else wT
         if use_mfma(a, wT):
             C = _C()
             out, _ = C.gemm(a, wT, C.EPI_RESID, None, r2)
             return out.view(*dy.shape[:-1], w.shape[1])
-    return torch.addmm(r2, a, w).view(*dy.shape[:-1], w.shape[1])
+    return torch.addmm(_here(a, r2), a, w).view(*dy.shape[:-1], w.shape[1])
 
 
 def dgrad_dgelu(dy, w, h, bias_dtype, wT=None, act=ACT_GELU, f8=None, bias_grad_out=None, q8=None):
@@ -241,13 +263,14 @@ def dgrad_dgelu(dy, w, h, bias_dtype, wT=None, act=ACT_GELU, f8=None, bias_grad_
         if f8 is not None else None
     if r is not None:
         return r
-    if _MODE != "blas" and a.is_cuda and h2.is_contiguous() and h2.dtype == a.dtype:
+    if (_MODE != "blas" and a.is_cuda and h2.is_contiguous() and h2.dtype == a.dtype and _fits(a, h2)
+            and _slot_ok(a, bias_grad_out, w.shape[1], bias_dtype)):
         wT = transpose(w) if wT is None else wT
         if use_mfma(a, wT):
             epi = C.EPI_DGELU_TANH if act == ACT_GELU_TANH else C.EPI_DGELU
             dh, db = C.gemm(a, wT, epi, None, h2, bias_dtype, bias_grad_out)
             return dh, db
     dg = torch.mm(a, w)
-    dh, _ = C.bias_act_bwd(dg, h2, None, act)
+    dh, _ = C.bias_act_bwd(dg, _here(a, h2).contiguous(), None, act)
     db = C.colsum(dh, bias_dtype) if bias_dtype is not None else None
     return dh, db

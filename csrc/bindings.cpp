@@ -648,8 +648,10 @@ Tensor k_splitk_reduce(Tensor slabs, at::ScalarType out_dtype, const c10::option
   TORCH_CHECK(slabs.is_cuda() && slabs.scalar_type() == at::kFloat && slabs.dim() >= 2, "splitk_reduce: fp32 slabs");
   Tensor sc = slabs.contiguous();
   Tensor out = out_or_empty(out_opt, sc.sizes().slice(1), sc.options().dtype(out_dtype), "splitk_reduce");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(sc.data_ptr()) % 16 == 0 && (out.numel() % 4 == 0 || sc.size(0) == 1),
-              "splitk_reduce: alignment");
+  // (the kernel loads the slabs and stores out with 16-byte vectors)
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(sc.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0 &&
+                  (out.numel() % 4 == 0 || sc.size(0) == 1),
+              "splitk_reduce: slabs and out must be 16-byte aligned");
   TORCH_CHECK(!accumulate || (out_opt.has_value() && out_dtype == at::kFloat),
               "splitk_reduce: accumulate needs an fp32 out");
   check(apex::splitk_reduce(sc.data_ptr<float>(), out.data_ptr(), out.numel(), (int)sc.size(0), dt_code(out_dtype),
@@ -1231,8 +1233,15 @@ Tensor k_input_normalize(Tensor x, std::vector<double> mean, std::vector<double>
 // MFMA GEMM (gemm.hip): C = epi(A[M,K] . B[N,K]^T). Returns [C, H] (H: pre-activation for
 // EPI_BIAS_GELU, gelu'(H) for EPI_BIAS_GELU_D) or [C, dbias] (EPI_DGELU, EPI_MUL). A may be any [..., K] view with a unit inner stride.
 // ---------------------------------------------------------------------------
+// an epilogue operand (bias, [M, N] input) the kernels may read: on a's device, 16-byte aligned (they
+// read it with 16-byte flat and buffer loads; the persistent kernel's descriptor starts at bias + n0 + wc * 64)
+bool gemm_operand_ok(const Tensor& a, const Tensor& t) {
+  return t.device() == a.device() && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+
 bool k_gemm_supported(Tensor a, Tensor b) {
-  if (!a.is_cuda() || a.dim() < 2 || b.dim() != 2 || a.scalar_type() != b.scalar_type()) return false;
+  if (!a.is_cuda() || b.device() != a.device() || a.dim() < 2 || b.dim() != 2 || a.scalar_type() != b.scalar_type())
+    return false;
   if (a.scalar_type() != at::kBFloat16 && a.scalar_type() != at::kHalf) return false;
   if (a.stride(-1) != 1 || b.stride(1) != 1) return false;
   const int64_t K = a.size(-1), N = b.size(0);
@@ -1273,8 +1282,8 @@ std::vector<Tensor> k_gemm(Tensor a, Tensor b, int64_t epi, const c10::optional<
   TORCH_CHECK(epi >= 0 && epi <= apex::EPI_MUL && epi != apex::EPI_F32, "gemm: bad epilogue ", epi);
   if (epi == apex::EPI_BIAS || gelu_fwd) {
     TORCH_CHECK(bias.has_value() && bias->defined() && bias->is_contiguous() && bias->numel() == N &&
-                    bias->scalar_type() == a.scalar_type(),
-                "gemm: bias must be a contiguous [N] tensor of the operand dtype");
+                    bias->scalar_type() == a.scalar_type() && gemm_operand_ok(a, *bias),
+                "gemm: bias must be a contiguous, 16-byte aligned [N] tensor of the operand dtype on a's device");
     g.bias = bias->data_ptr();
   }
   if (gelu_fwd) {
@@ -1284,18 +1293,25 @@ std::vector<Tensor> k_gemm(Tensor a, Tensor b, int64_t epi, const c10::optional<
   Tensor part;
   if (dgelu || epi == apex::EPI_RESID) {
     TORCH_CHECK(aux.has_value() && aux->defined() && aux->scalar_type() == a.scalar_type() &&
-                    aux->numel() == M * N && aux->stride(-1) == 1 && aux->is_contiguous(),
-                "gemm: aux must be a contiguous [M, N] tensor of the operand dtype");
+                    (aux->sizes() == at::IntArrayRef(osz) || aux->sizes() == at::IntArrayRef({M, N})) &&
+                    aux->is_contiguous() && gemm_operand_ok(a, *aux),
+                "gemm: aux must be a contiguous, 16-byte aligned [M, N] (or C-shaped) tensor of the operand dtype on "
+                "a's device");
     g.aux = aux->data_ptr();
     g.ldaux = N;
   }
   if (dgelu) {
     part = at::empty({apex::gemm_part_rows((int)M), N}, a.options().dtype(at::kFloat));
     g.part = part.data_ptr<float>();
+    // the bias gradient's destination is checked before anything is launched (partial_colsum stores
+    // scalars: a slot needs no more than its element alignment, which every view has)
+    if (bias_grad_dtype.has_value()) {
+      dt_code(*bias_grad_dtype);
+      extra = out_or_empty(bias_grad_out, {N}, a.options().dtype(*bias_grad_dtype), "gemm bias grad");
+    }
   }
   check(apex::gemm_nt(g, dt_code(a.scalar_type()), cur_stream()), "gemm");
   if (dgelu && bias_grad_dtype.has_value()) {
-    extra = out_or_empty(bias_grad_out, {N}, a.options().dtype(*bias_grad_dtype), "gemm bias grad");
     check(apex::gemm_bias_grad(part.data_ptr<float>(), (int)part.size(0), (int)N, extra.data_ptr(),
                                dt_code(*bias_grad_dtype), cur_stream()),
           "gemm_bias_grad");
@@ -1510,7 +1526,8 @@ void k_fp8_update_scales(Tensor hist, Tensor amax_cur, Tensor scale, Tensor scal
 // weight gradient: out[P, Q] = a^T b for a [R, P], b [R, Q] (contraction over the R rows, split
 // into `splits` slices whose fp32 partials are combined by splitk_reduce)
 bool k_gemm_tt_supported(Tensor a, Tensor b, int64_t splits) {
-  if (!a.is_cuda() || a.dim() != 2 || b.dim() != 2 || a.scalar_type() != b.scalar_type()) return false;
+  if (!a.is_cuda() || b.device() != a.device() || a.dim() != 2 || b.dim() != 2 || a.scalar_type() != b.scalar_type())
+    return false;
   if (a.scalar_type() != at::kBFloat16 && a.scalar_type() != at::kHalf) return false;
   if (!a.is_contiguous() || !b.is_contiguous() || a.size(0) != b.size(0)) return false;
   auto al = [](const Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; };
@@ -1531,8 +1548,15 @@ Tensor k_gemm_tt(Tensor a, Tensor b, int64_t splits, at::ScalarType out_dtype, c
   g.ldb = Q;
   g.ldc = Q;
   g.splits = (int)splits;
+  // out_dtype, and out (a gradient-bucket slot: splitk_reduce stores 16-byte vectors), are checked before
+  // the GEMM is launched
+  dt_code(out_dtype);
+  if (out_opt.has_value() && out_opt->defined())
+    TORCH_CHECK(out_opt->device() == a.device() && out_opt->is_contiguous() && out_opt->scalar_type() == out_dtype &&
+                    out_opt->numel() == P * Q && reinterpret_cast<uintptr_t>(out_opt->data_ptr()) % 16 == 0,
+                "gemm_tt: out must be a contiguous, 16-byte aligned tensor of P * Q elements of out_dtype on a's device");
   Tensor out;
-  if (splits == 1 && out_dtype == a.scalar_type() && !out_opt) {
+  if (splits == 1 && out_dtype == a.scalar_type() && !(out_opt.has_value() && out_opt->defined())) {
     out = at::empty({P, Q}, a.options());
     g.C = out.data_ptr();
     g.epi = apex::EPI_NONE;
@@ -1591,7 +1615,7 @@ Tensor k_gemm_tt_f8(Tensor a, Tensor b, Tensor alpha_a, Tensor alpha_b, int64_t 
 void k_gemm_tt_acc(Tensor a, Tensor b, Tensor out) {
   TORCH_CHECK(k_gemm_tt_supported(a, b, 1), "gemm_tt_acc: unsupported operands");
   const int64_t P = a.size(1), Q = b.size(1);
-  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat && out.is_contiguous() && out.dim() == 2 &&
+  TORCH_CHECK(out.device() == a.device() && out.scalar_type() == at::kFloat && out.is_contiguous() && out.dim() == 2 &&
                   out.size(0) == P && out.size(1) == Q && reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
               "gemm_tt_acc: out must be a contiguous fp32 [P, Q] tensor");
   apex::GemmArgs g{};
@@ -1621,7 +1645,8 @@ Tensor k_partial_colsum(Tensor part, at::ScalarType out_dtype, const c10::option
 }
 
 Tensor k_transpose(Tensor x) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2, "transpose: 2-D device tensor");
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && (x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf),
+              "transpose: 2-D bf16 / fp16 device tensor");
   Tensor xc = x.contiguous();
   if (reinterpret_cast<uintptr_t>(xc.data_ptr()) % 16 != 0) xc = xc.clone();
   Tensor out = at::empty({xc.size(1), xc.size(0)}, xc.options());
