@@ -142,6 +142,22 @@ def _pad_last(t, n):
     return F.pad(t, (0, n - t.shape[-1])) if t.shape[-1] != n else t
 
 
+def _kernel_view(t):
+    """``t`` as the flash binding takes it: last dim contiguous, every other stride a multiple of 8
+    elements, 16-byte aligned. Any other view (a slice that starts off a 16-byte boundary, a head dim
+    cut out of a wider one) is copied to a contiguous tensor, as apex.ops.fused's ``_wgrad`` does for an
+    unaligned slot; the copy is differentiable, so the gradient still reaches the view."""
+    ok = t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:-1]) and t.data_ptr() % 16 == 0
+    return t if ok else t.clone(memory_format=torch.contiguous_format)
+
+
+def _kernel_k_lens(k_lens, device):
+    """Key lengths as the kernels read them: a contiguous int32 tensor on the operands' device."""
+    if k_lens is None:
+        return None
+    return torch.as_tensor(k_lens).to(device=device, dtype=torch.int32).contiguous()
+
+
 def attention_packed(qkv, attn_bias=None, dropout_p=0.0, causal=False, scale=None, k_lens=None):
     B, S, three, h, d = qkv.shape
     scale = 1.0 / math.sqrt(d) if scale is None else scale
@@ -149,9 +165,10 @@ def attention_packed(qkv, attn_bias=None, dropout_p=0.0, causal=False, scale=Non
         from . import flash
 
         bias = prepare_bias(attn_bias, B, h, S, S, qkv.dtype)
+        k_lens = _kernel_k_lens(k_lens, qkv.device)
         dp = _padded_dim(d)
         if dp == d:
-            return flash.flash_attention_packed(qkv, dropout_p, causal, scale, k_lens, bias)
+            return flash.flash_attention_packed(_kernel_view(qkv), dropout_p, causal, scale, k_lens, bias)
         o = flash.flash_attention_packed(_pad_last(qkv, dp), dropout_p, causal, scale, k_lens, bias)
         return o[..., :d]
     q, k, v = qkv.unbind(2)
@@ -194,9 +211,10 @@ def attention_grouped_packed(qkv, num_heads, num_kv_heads, attn_bias=None, dropo
         from . import flash
 
         bias = prepare_bias(attn_bias, B, H, S, S, qkv.dtype)
+        k_lens = _kernel_k_lens(k_lens, qkv.device)
         dp = _padded_dim(d)
         if dp == d:
-            return flash.flash_attention_grouped_packed(qkv, H, Hk, dropout_p, causal, scale, k_lens, bias)
+            return flash.flash_attention_grouped_packed(_kernel_view(qkv), H, Hk, dropout_p, causal, scale, k_lens, bias)
         o = flash.flash_attention_grouped_packed(_pad_last(qkv, dp), H, Hk, dropout_p, causal, scale, k_lens, bias)
         return o[..., :d]
     q, k, v = qkv[:, :, :H], qkv[:, :, H:H + Hk], qkv[:, :, H + Hk:]
@@ -214,9 +232,11 @@ def attention(q, k, v, attn_bias=None, dropout_p=0.0, causal=False, scale=None, 
         from . import flash
 
         bias = prepare_bias(attn_bias, B, h, Sq, k.shape[1], q.dtype)
+        k_lens = _kernel_k_lens(k_lens, q.device)
         dp = _padded_dim(d)
         if dp == d:
-            return flash.flash_attention(q, k, v, dropout_p, causal, scale, k_lens, bias)
+            return flash.flash_attention(_kernel_view(q), _kernel_view(k), _kernel_view(v), dropout_p, causal, scale,
+                                         k_lens, bias)
         o = flash.flash_attention(_pad_last(q, dp), _pad_last(k, dp), _pad_last(v, dp), dropout_p, causal, scale,
                                   k_lens, bias)
         return o[..., :d]

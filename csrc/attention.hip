@@ -46,6 +46,14 @@ int attn_fwd(const AttnArgs& a, int dt, hipStream_t s) {
 // Two-kernel backward (key-stationary dK/dV + query-stationary dQ, delta pre-pass) for key ranges
 // longer than one 128-key block
 bool attn_bwd_needs_dq_acc(const AttnArgs& a) { return a.Sk > kBwdBK; }
+bool attn_bwd_two_kernel(int Sk) { return Sk > kBwdBK; }
+int attn_fwd_loop_id(int D, int Sk, bool dropout, bool bias) {
+  switch (attn_fwd_loop(D, Sk, dropout, bias)) {
+    case FwdLoop::kShort: return 0;
+    case FwdLoop::kDoubleBuffered: return 1;
+    default: return 2;
+  }
+}
 
 int attn_bwd(const AttnArgs& a, const void* dout, float* delta_ws, void* dk, void* dv, int dt,
              hipStream_t s) {

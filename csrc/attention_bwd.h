@@ -27,6 +27,20 @@ __global__ void __launch_bounds__(256) attn_bwd_delta_kernel(AttnArgs a, const v
   if (q < a.Sq && (idx % CPR) == 0) delta[(int64_t)bh * a.Sq + q] = part;
 }
 
+// DSUM adds up the gradients AS STORED. For fp16 the compiler (fp-contract=fast) otherwise forms the
+// two copies of (T)(x * mul) differently: the stored one as v_mul_f32 + v_cvt_pk_f16_f32 (the product
+// rounded to fp32, then to fp16), the summed one as v_fma_mixlo_f16 (the exact product rounded to fp16
+// once). Where the product lies next to an fp16 rounding midpoint they are one fp16 ulp apart, and the
+// column sum is off by that ulp (2**-11 for an element in [0.5, 1): tests/test_attn_numerics_gpu.py).
+// The fp32 product is made opaque here, so one conversion serves both. (bf16 has no mixed-precision
+// FMA: both copies already come from the same fp32 product.)
+template <typename T, bool DSUM>
+__device__ __forceinline__ T stored_product(float x, float mul) {
+  float p = x * mul;
+  if constexpr (DSUM && std::is_same_v<T, f16>) asm volatile("" : "+v"(p));
+  return (T)p;
+}
+
 // DQ = true (Sk <= 128: the workgroup holds every key, so it is the sole owner of dQ for its
 // query rows and writes it directly; delta is computed here from O). DQ = false (longer key
 // ranges): dK/dV only, delta read from attn_bwd_delta_kernel's output, and attn_bwd_dq_kernel
@@ -384,7 +398,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D <= 6
       for (int t = 0; t < NT; ++t) {
         t4 w;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) w[i] = (T)(acc[t][i] * a.scale);
+        for (int i = 0; i < 4; ++i) w[i] = stored_product<T, DSUM>(acc[t][i], a.scale);
         wq[t] = __builtin_bit_cast(uint2, w);
       }
       // 16-byte stores (as the forward's O, T21): lanes of 16-lane rows lg and lg + 1 hold 4 dims each
@@ -496,7 +510,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D <= 6
         t4 w;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          w[e] = (T)(acc[db][4 * g4 + e] * mul);
+          w[e] = stored_product<T, DSUM>(acc[db][4 * g4 + e], mul);
           if constexpr (DSUM) sum += (k0 + kl0 + e < a.Sk) ? (float)w[e] : 0.f;
         }
         *(t4*)(lds_k + (32 * db + r) * LDE + kl0) = w;
@@ -785,7 +799,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D <= 6
     for (int g = 0; g < 4; ++g) {
       t4 w;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) w[e] = (T)(dq[db][4 * g + e] * a.scale);
+      for (int e = 0; e < 4; ++e) w[e] = stored_product<T, DSUM>(dq[db][4 * g + e], a.scale);
       wv[g] = __builtin_bit_cast(uint2, w);
     }
 #pragma unroll

@@ -3,6 +3,7 @@
 #include <ATen/hip/HIPContext.h>
 #include <torch/extension.h>
 
+#include <limits>
 #include <vector>
 
 #include "kernels.h"
@@ -320,11 +321,21 @@ void attn_set(apex::AttnArgs& a, const Tensor& t, int64_t& bs, int64_t& ss, int6
   hs = t.stride(2);
 }
 
+// every tensor a kernel dereferences lives on q's device (a CPU tensor's host pointer, or another
+// GPU's, would reach the kernel otherwise): checked before anything is launched
+void attn_on_device(const Tensor& q, const Tensor& t, const char* what) {
+  TORCH_CHECK(q.is_cuda(), "flash attention: q must be a device tensor");
+  TORCH_CHECK(t.is_cuda() && t.device() == q.device(), "flash attention: ", what, " must be on q's device (", q.device(),
+              "), got ", t.device());
+}
+
 apex::AttnArgs attn_common(const Tensor& q, const Tensor& k, const Tensor& v, bool causal,
                            double scale, double p_drop, int64_t seed, int64_t offset,
                            const c10::optional<Tensor>& k_lens) {
   apex::AttnArgs a{};
   TORCH_CHECK(q.scalar_type() == k.scalar_type() && q.scalar_type() == v.scalar_type(), "dtype mismatch");
+  attn_on_device(q, k, "k");
+  attn_on_device(q, v, "v");
   a.q = q.data_ptr();
   a.k = k.data_ptr();
   a.v = v.data_ptr();
@@ -356,7 +367,9 @@ apex::AttnArgs attn_common(const Tensor& q, const Tensor& k, const Tensor& v, bo
   a.seed = (uint64_t)seed;
   a.offset = (uint64_t)offset;
   if (k_lens.has_value() && k_lens->defined()) {
-    TORCH_CHECK(k_lens->scalar_type() == at::kInt && k_lens->numel() == a.B, "k_lens must be int32 [B]");
+    TORCH_CHECK(k_lens->scalar_type() == at::kInt && k_lens->numel() == a.B && k_lens->is_contiguous(),
+                "k_lens must be int32 [B]");
+    attn_on_device(q, *k_lens, "k_lens");
     a.k_lens = k_lens->data_ptr<int>();
   }
   return a;
@@ -368,11 +381,14 @@ void attn_set_bias(apex::AttnArgs& a, const c10::optional<Tensor>& bias, const T
   if (!bias.has_value() || !bias->defined()) return;
   const Tensor& t = *bias;
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == q.scalar_type(), "attention bias must be a device tensor in q's dtype");
+  attn_on_device(q, t, "the bias");
   TORCH_CHECK(t.dim() == 4 && t.size(3) == a.Sk && t.stride(3) == 1, "attention bias must be [B|1, H|1, Sq|1, Sk], key-contiguous");
   TORCH_CHECK((t.size(0) == a.B || t.stride(0) == 0 || t.size(0) == 1) && (t.size(1) == a.H || t.size(1) == 1 || t.stride(1) == 0) &&
                   (t.size(2) == a.Sq || t.size(2) == 1 || t.stride(2) == 0),
               "attention bias does not broadcast to [B, H, Sq, Sk]");
-  TORCH_CHECK(((uintptr_t)t.data_ptr() & 7) == 0 && t.stride(2) % 4 == 0 && t.stride(1) % 4 == 0 && t.stride(0) % 4 == 0,
+  // (the stride of a broadcast dim is not used: a [1, 1, 1, Sk] bias with Sk % 4 != 0 is as good as any)
+  auto row_ok = [&](int d) { return t.size(d) == 1 || t.stride(d) % 4 == 0; };
+  TORCH_CHECK(((uintptr_t)t.data_ptr() & 7) == 0 && row_ok(2) && row_ok(1) && row_ok(0),
               "attention bias rows must be 8-byte aligned");
   TORCH_CHECK(t.scalar_type() != at::kFloat || ((uintptr_t)t.data_ptr() & 15) == 0,
               "fp32 attention bias rows must be 16-byte aligned");
@@ -426,6 +442,12 @@ std::vector<Tensor> flash_attn_fwd(Tensor q, Tensor k, Tensor v, bool causal, do
   } else {
     dmask = at::empty({0}, q.options().dtype(at::kShort));
   }
+  if (a.Sk == 0) {  // no key: every row is fully masked (O = 0, lse = +inf), nothing to launch
+    TORCH_CHECK(!a.q8o, "flash_attn_fwd: the fp8 code output is not supported with an empty key range");
+    o.zero_();
+    lse.fill_(std::numeric_limits<float>::infinity());
+    return {o, lse, dmask};
+  }
   check(apex::attn_fwd(a, dt_code(q.scalar_type()), cur_stream()), "attn_fwd");
   return {o, lse, dmask};
 }
@@ -469,6 +491,21 @@ bool flash_attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor 
   apex::AttnArgs a = attn_common(q, k, v, causal, scale, p_drop, seed, offset, k_lens);
   a.dbg = (int)dbg;
   attn_set_bias(a, bias, q);
+  // everything the kernels read or write besides q / k / v: device, dtype, sizes, before any launch
+  attn_on_device(q, dout, "dout");
+  attn_on_device(q, o, "o");
+  attn_on_device(q, lse, "lse");
+  attn_on_device(q, dq, "dq");
+  attn_on_device(q, dk, "dk");
+  attn_on_device(q, dv, "dv");
+  TORCH_CHECK(o.sizes() == q.sizes() && dout.sizes() == q.sizes() && o.scalar_type() == q.scalar_type() &&
+                  dout.scalar_type() == q.scalar_type(),
+              "flash_attn_bwd: o / dout must have the sizes and dtype of q");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.dim() == 3 && lse.size(0) == a.B && lse.size(1) == a.H &&
+                  lse.size(2) == a.Sq && lse.is_contiguous(),
+              "flash_attn_bwd: lse must be a contiguous fp32 [B, H, Sq] tensor (the forward's)");
+  if (dbias.has_value() && dbias->defined()) attn_on_device(q, *dbias, "dbias");
+  if (dsum.has_value() && dsum->defined()) attn_on_device(q, *dsum, "dsum");
   if (dbias.has_value() && dbias->defined()) {
     // gradient of a trainable bias: a zeroed fp32 tensor with the bias's sizes, contiguous; the
     // kernels add dS into it (atomically where the bias broadcasts over batch, heads or queries)
@@ -485,6 +522,7 @@ bool flash_attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor 
   }
   TORCH_CHECK(!(a.bias && dsum.has_value() && dsum->defined()), "flash_attn_bwd: dsum with a score bias is not supported");
   if (dsum.has_value() && dsum->defined()) {
+    TORCH_CHECK(q.scalar_type() != at::kFloat, "flash_attn_bwd: dsum is a feature of the 16-bit units (fp32 operands)");
     TORCH_CHECK(dsum->is_cuda() && dsum->scalar_type() == at::kFloat && dsum->is_contiguous() &&
                     dsum->numel() == (int64_t)a.B * 3 * a.H * a.D,
                 "flash_attn_bwd: dsum must be a zeroed fp32 [B, 3, H, D] tensor");
@@ -520,9 +558,20 @@ bool flash_attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor 
   a.dq = dq.data_ptr();
   a.mask_words = 2 * (((int64_t)a.Sk + 31) / 32);
   if (a.drop_thresh) {
-    TORCH_CHECK(dmask.has_value() && dmask->numel() == (int64_t)a.B * a.H * a.Sq * a.mask_words,
-                "flash_attn_bwd: dropout mask from the forward pass is required");
+    TORCH_CHECK(dmask.has_value() && dmask->defined() && dmask->scalar_type() == at::kShort && dmask->is_contiguous() &&
+                    dmask->numel() == (int64_t)a.B * a.H * a.Sq * a.mask_words && ((uintptr_t)dmask->data_ptr() & 3) == 0,
+                "flash_attn_bwd: dropout mask from the forward pass is required (int16, B * H * Sq * mask words)");
+    attn_on_device(q, *dmask, "dmask");
     a.dmask = (uint16_t*)dmask->data_ptr();
+  }
+  if ((int64_t)a.B * a.H * a.Sq == 0 || a.Sk == 0) {
+    TORCH_CHECK(!(q8_dq.has_value() && q8_dq->defined()) && !q8_only,
+                "flash_attn_bwd: the fp8 code outputs are not supported with an empty query or key range");
+    // no query or no key: P is empty, every gradient is zero (dbias / dsum arrive zeroed); nothing to launch
+    dq.zero_();
+    dk.zero_();
+    dv.zero_();
+    return false;
   }
   const int64_t rows = (int64_t)a.B * a.H * a.Sq;
   Tensor delta_ws;  // rowsum(dO * O), one pre-pass kernel, read by the dK/dV and dQ kernels
@@ -1191,7 +1240,10 @@ void k_lse_merge(Tensor acc_o, Tensor acc_lse, Tensor o, Tensor lse, bool first,
 
 Tensor flash_dropout_mask(int64_t B, int64_t H, int64_t Sq, int64_t Sk, double p_drop, int64_t seed,
                           int64_t offset, at::Device dev) {
+  TORCH_CHECK(dev.is_cuda(), "flash_dropout_mask: a GPU device is required");
+  TORCH_CHECK(B >= 0 && H >= 0 && Sq >= 0 && Sk >= 0, "flash_dropout_mask: negative size");
   Tensor out = at::empty({B, H, Sq, Sk}, at::TensorOptions().dtype(at::kByte).device(dev));
+  if (out.numel() == 0) return out;
   const uint32_t th = apex::attn_drop_thresh(p_drop);
   check(apex::attn_dropout_mask(out.data_ptr<uint8_t>(), B * H, (int)Sq, (int)Sk, (uint64_t)seed,
                                 (uint64_t)offset, th, cur_stream()),
@@ -1716,6 +1768,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_kv_group_reduce", &attn_kv_group_reduce, py::arg("dk_x"), py::arg("dv_x"), py::arg("dk"), py::arg("dv"));
   m.def("partial_colsum", &k_partial_colsum, py::arg("part"), py::arg("out_dtype"), py::arg("out") = py::none());
   m.def("flash_dropout_mask", &flash_dropout_mask);
+  // host-only: which forward K/V loop ("short", "double_buffered", "two_barrier") and which backward
+  // scheme a 16-bit launch takes (the tests assert that their cases reach every instantiation)
+  m.def("attn_fwd_loop", [](int64_t D, int64_t Sk, bool dropout, bool bias) -> std::string {
+    static const char* names[] = {"short", "double_buffered", "two_barrier"};
+    return names[apex::attn_fwd_loop_id((int)D, (int)Sk, dropout, bias)];
+  }, py::arg("D"), py::arg("Sk"), py::arg("dropout"), py::arg("bias"));
+  m.def("attn_bwd_two_kernel", [](int64_t Sk) { return apex::attn_bwd_two_kernel((int)Sk); }, py::arg("Sk"));
   m.def("lse_merge", &k_lse_merge, py::arg("acc_o"), py::arg("acc_lse"), py::arg("o"), py::arg("lse"),
         py::arg("first"), py::arg("s0") = 0);
   m.def("weight_norm_fwd", &k_wn_fwd);

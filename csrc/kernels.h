@@ -135,6 +135,11 @@ inline uint32_t attn_drop_thresh(double p) {  // 8-bit keep threshold in [1, 255
 }
 int attn_fwd(const AttnArgs& a, int dt, hipStream_t s);
 bool attn_bwd_needs_dq_acc(const AttnArgs& a);
+// host-only views of the launch decisions (16-bit units), for the tests' path-coverage assertions:
+// attention_impl.h's attn_fwd_loop as 0 = single-stage short, 1 = double-buffered, 2 = two-barrier;
+// whether a key range takes the delta + dK/dV + dQ kernels instead of the fused backward
+int attn_fwd_loop_id(int D, int Sk, bool dropout, bool bias);
+bool attn_bwd_two_kernel(int Sk);
 // delta_ws: [B*H*Sq] fp32 workspace when attn_bwd_needs_dq_acc (two-kernel backward)
 int attn_bwd(const AttnArgs& a, const void* dout, float* delta_ws, void* dk, void* dv, int dt,
              hipStream_t s);
