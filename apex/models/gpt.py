@@ -27,6 +27,10 @@ from ..transformer.functional import fused_rope
 # APEX_GPT_FUSED_LN=0: per-block forward (separate LayerNorms; A/B and fallback switch)
 _FUSED_LN = os.environ.get("APEX_GPT_FUSED_LN", "1") != "0"
 
+# GPTConfig.activation -> the gated activation's code (None: the plain bias + GELU(tanh) MLP)
+_ACTIVATIONS = {"gelu": None, "swiglu": fops.ACT_SILU, "geglu": fops.ACT_GELU_TANH}
+
+
 @dataclass
 class GPTConfig:
     vocab_size: int = 50257
@@ -42,8 +46,12 @@ class GPTConfig:
     rotary_percent: float = 1.0
     rotary_base: int = 10000
     n_kv_head: int | None = None  # grouped-query attention: key/value heads (None = n_head)
+    activation: str = "gelu"  # "gelu" | "swiglu" | "geglu" (gated: c_fc emits [gate | up], tanh GELU)
+    ffn_hidden_size: int | None = None  # MLP width (None = 4 * n_embd)
 
     def __post_init__(self):
+        if self.activation not in _ACTIVATIONS:
+            raise ValueError(f"activation must be 'gelu', 'swiglu' or 'geglu', got {self.activation!r}")
         if self.n_kv_head is not None and (self.n_kv_head < 1 or self.n_head % self.n_kv_head):
             raise ValueError(f"n_head={self.n_head} must be a multiple of n_kv_head={self.n_kv_head}")
         if self.position_embedding_type not in ("learned", "rope"):
@@ -79,8 +87,11 @@ class GPTBlock(nn.Module):
         self.c_attn = nn.Linear(c.n_embd, 3 * c.n_embd if self.hk == self.h else (self.h + 2 * self.hk) * self.d)
         self.c_proj = nn.Linear(c.n_embd, c.n_embd)
         self.ln_2 = FusedLayerNorm(c.n_embd, eps=c.layer_norm_eps)
-        self.c_fc = nn.Linear(c.n_embd, 4 * c.n_embd)
-        self.mlp_proj = nn.Linear(4 * c.n_embd, c.n_embd)
+        ffn = 4 * c.n_embd if c.ffn_hidden_size is None else c.ffn_hidden_size
+        # gated MLP (swiglu / geglu): c_fc emits [gate | up], 2 * ffn wide, and mlp_proj takes their ffn-wide product
+        self.gated_act = _ACTIVATIONS[c.activation]
+        self.c_fc = nn.Linear(c.n_embd, ffn if self.gated_act is None else 2 * ffn)
+        self.mlp_proj = nn.Linear(ffn, c.n_embd)
         self.p = c.dropout
 
     def _rotate(self, qkv, rope):
@@ -96,6 +107,21 @@ class GPTBlock(nn.Module):
             qkv = fused_rope.apply_rotary_qkv_grouped(qkv, rope[0], rope[1], self.h, self.hk)
         return fops.attention_qkv_grouped(qkv, self.h, self.hk, None, p, causal=True).reshape(B, S, E)
 
+    def _mlp(self, xn):
+        """The MLP up to mlp_proj's bias (added by the residual update that follows)."""
+        if self.gated_act is not None:
+            # GEMM -> one gated-activation kernel (bias folded in) -> GEMM. Under apex.fp8.fp8_autocast
+            # fused_dense never hands back a codes-only tensor: only apex.ops.blocks' whole-sublayer
+            # Functions ask a producer for one (Fp8State.codes_only_ok), fused_dense calls gemm.linear /
+            # gemm.dgrad without a q8 request, and this path does not go through fblocks.
+            h = fops.fused_dense(xn, self.c_fc.weight, None)
+            return fops.fused_dense(fops.gated_act(h, self.c_fc.bias, self.gated_act), self.mlp_proj.weight, None)
+        t = fblocks.mlp(xn, self.c_fc.weight, self.c_fc.bias, self.mlp_proj.weight, fops.ACT_GELU_TANH)
+        if t is None:
+            h = fops.dense_act(xn, self.c_fc.weight, self.c_fc.bias, fops.ACT_GELU_TANH)
+            t = fops.fused_dense(h, self.mlp_proj.weight, None)
+        return t
+
     def forward(self, x, rope=None):
         B, S, E = x.shape
         p = self.p if self.training else 0.0
@@ -107,10 +133,7 @@ class GPTBlock(nn.Module):
             ctx = fops.attention_qkv_packed(qkv, None, p, causal=True).reshape(B, S, E)
         x = fops.bias_dropout_add(fops.fused_dense(ctx, self.c_proj.weight, None), self.c_proj.bias, x, p)
         xn = self.ln_2(x)
-        t = fblocks.mlp(xn, self.c_fc.weight, self.c_fc.bias, self.mlp_proj.weight, fops.ACT_GELU_TANH)
-        if t is None:
-            h = fops.dense_act(xn, self.c_fc.weight, self.c_fc.bias, fops.ACT_GELU_TANH)
-            t = fops.fused_dense(h, self.mlp_proj.weight, None)
+        t = self._mlp(xn)
         return fops.bias_dropout_add(t, self.mlp_proj.bias, x, p)
 
     def forward_fused(self, x, xn, nxt, rope=None):
@@ -129,10 +152,7 @@ class GPTBlock(nn.Module):
             ctx = fops.attention_qkv_packed(qkv, None, p, causal=True).reshape(B, S, E)
         x, xn = fops.bias_dropout_add_ln(fops.fused_dense(ctx, self.c_proj.weight, None), self.c_proj.bias, x,
                                          self.ln_2.weight, self.ln_2.bias, p, self.ln_2.eps)
-        t = fblocks.mlp(xn, self.c_fc.weight, self.c_fc.bias, self.mlp_proj.weight, fops.ACT_GELU_TANH)
-        if t is None:
-            h = fops.dense_act(xn, self.c_fc.weight, self.c_fc.bias, fops.ACT_GELU_TANH)
-            t = fops.fused_dense(h, self.mlp_proj.weight, None)
+        t = self._mlp(xn)
         return fops.bias_dropout_add_ln(t, self.mlp_proj.bias, x, nxt.weight, nxt.bias, p, nxt.eps)
 
 

@@ -32,6 +32,10 @@ from ..transformer.functional import fused_rope
 # APEX_MEGATRON_FUSED_LN=0: per-layer forward (separate LayerNorms; A/B and fallback switch)
 _FUSED_LN = os.environ.get("APEX_MEGATRON_FUSED_LN", "1") != "0"
 
+# MegatronGPTConfig.activation -> the gated activation's code (None: the plain bias + GELU(erf) MLP)
+_ACTIVATIONS = {"gelu": None, "swiglu": fops.ACT_SILU, "geglu": fops.ACT_GELU}
+
+
 @dataclass
 class MegatronGPTConfig:
     vocab_size: int = 50304
@@ -49,8 +53,11 @@ class MegatronGPTConfig:
     rotary_percent: float = 1.0
     rotary_base: int = 10000
     num_query_groups: int | None = None  # grouped-query attention: key/value heads (None = num_attention_heads)
+    activation: str = "gelu"  # "gelu" | "swiglu" | "geglu" (gated: dense_h_to_4h emits [gate | up], erf GELU)
 
     def __post_init__(self):
+        if self.activation not in _ACTIVATIONS:
+            raise ValueError(f"activation must be 'gelu', 'swiglu' or 'geglu', got {self.activation!r}")
         g = self.num_query_groups
         if g is not None and (g < 1 or self.num_attention_heads % g):
             raise ValueError(f"num_attention_heads={self.num_attention_heads} must be a multiple of "
@@ -79,6 +86,11 @@ def _tp_rng():
 
 
 class ParallelTransformerLayer(nn.Module):
+    # Gated MLP (activation "swiglu" / "geglu"): dense_h_to_4h is [2 * ffn_hidden_size, hidden] and every
+    # rank's shard of it (and of its bias) is laid out rank-locally as its ffn/tp gate rows, then its
+    # ffn/tp up rows, the rule the query_key_value shard follows for Q / K / V. gated_act on the local
+    # [.., 2 ffn/tp] output therefore pairs each gate column with its own up column and needs nothing
+    # from the TP group; the TP = 1 weight is [cat_r(gate_r); cat_r(up_r)].
     def __init__(self, c: MegatronGPTConfig, layer_number):
         super().__init__()
         tpws = ps.get_tensor_model_parallel_world_size()
@@ -99,7 +111,12 @@ class ParallelTransformerLayer(nn.Module):
         self.dense = tp.RowParallelLinear(c.hidden_size, c.hidden_size, input_is_parallel=True,
                                           init_method=_init(out_std), skip_bias_add=True, params_dtype=c.params_dtype)
         self.post_attention_layernorm = FusedLayerNorm(c.hidden_size, eps=c.layernorm_epsilon)
-        self.dense_h_to_4h = tp.ColumnParallelLinear(c.hidden_size, c.ffn_hidden_size, gather_output=False,
+        self.gated_act = _ACTIVATIONS[c.activation]
+        if self.gated_act is not None and c.ffn_hidden_size % tpws:
+            raise ValueError(f"ffn_hidden_size={c.ffn_hidden_size} must be a multiple of the tensor-parallel "
+                             f"world size {tpws}")
+        f1_out = c.ffn_hidden_size if self.gated_act is None else 2 * c.ffn_hidden_size
+        self.dense_h_to_4h = tp.ColumnParallelLinear(c.hidden_size, f1_out, gather_output=False,
                                                      init_method=_init(c.init_method_std), skip_bias_add=True,
                                                      params_dtype=c.params_dtype)
         self.dense_4h_to_h = tp.RowParallelLinear(c.ffn_hidden_size, c.hidden_size, input_is_parallel=True,
@@ -127,6 +144,13 @@ class ParallelTransformerLayer(nn.Module):
         with _tp_rng():
             return fops.attention_qkv_packed(qkv, None, pa, causal=True)
 
+    def _gated_mlp(self, xn):
+        # through the two parallel linears (their TP / sequence-parallel mappings), the rank-local
+        # [gate | up] shard between them; not fblocks.mlp. Under apex.fp8.fp8_autocast the linears'
+        # outputs are never codes-only: only apex.ops.blocks' whole-sublayer Functions request one.
+        h, b1 = self.dense_h_to_4h(xn)
+        return self.dense_4h_to_h(fops.gated_act(h, b1, self.gated_act))
+
     def forward(self, x, rope=None):
         B, S, _ = x.shape
         ph = self.p_hidden if self.training else 0.0
@@ -137,6 +161,9 @@ class ParallelTransformerLayer(nn.Module):
         x = fops.bias_dropout_add(out, bias, x, ph)
         xn = self.post_attention_layernorm(x)
         f1, f2 = self.dense_h_to_4h, self.dense_4h_to_h
+        if self.gated_act is not None:
+            out, bias = self._gated_mlp(xn)
+            return fops.bias_dropout_add(out, bias, x, ph)
         if not (f1.sequence_parallel_enabled or f2.sequence_parallel_enabled) and f1.bias is not None:
             # whole MLP shard as one Function (GEMM+bias+GELU epilogue, dGELU epilogue in backward)
             # between the same TP mappings the two parallel linears apply
@@ -163,7 +190,9 @@ class ParallelTransformerLayer(nn.Module):
         x, xn = fops.bias_dropout_add_ln(out, bias, x, ln2.weight, ln2.bias, ph, ln2.eps)
         f1, f2 = self.dense_h_to_4h, self.dense_4h_to_h
         t = bias2 = None
-        if not (f1.sequence_parallel_enabled or f2.sequence_parallel_enabled) and f1.bias is not None:
+        if self.gated_act is not None:
+            t, bias2 = self._gated_mlp(xn)
+        elif not (f1.sequence_parallel_enabled or f2.sequence_parallel_enabled) and f1.bias is not None:
             t = fblocks.mlp(tp.copy_to_tensor_model_parallel_region(xn), f1.weight, f1.bias, f2.weight)
             if t is not None:
                 t, bias2 = tp.reduce_from_tensor_model_parallel_region(t), f2.bias

@@ -12,6 +12,8 @@ the PyTorch reference formulation on CPU (also the numerics reference for the te
                                             y = LN(res + dropout(x W^T + b))  (one fused
                                                                      kernel each way)
   bias_dropout_add(x, b, res, p)            y = res + dropout(x + b)
+  gated_act(x, b, act)                      y = act(g + b_g) * (u + b_u), x = [g | u]  (SwiGLU / GEGLU:
+                                                                     bias_swiglu, bias_geglu)
   attention_qkv_packed / attention_qkv_grouped / softmax_cross_entropy
 
 Forward and input-gradient GEMMs run on the hand-written MFMA kernel (apex.ops.gemm, with
@@ -30,6 +32,7 @@ import torch.nn.functional as F
 from .. import _ext
 
 ACT_GELU, ACT_GELU_TANH, ACT_RELU, ACT_NONE = 0, 1, 2, 3
+ACT_SILU = 4
 
 
 def _seed(device=None):
@@ -376,6 +379,8 @@ def _act_ref(h, act):
         return F.gelu(h, approximate="tanh")
     if act == ACT_RELU:
         return F.relu(h)
+    if act == ACT_SILU:
+        return F.silu(h)
     return h
 
 
@@ -416,6 +421,88 @@ def bias_gelu(h, bias):
     if _native(h) and h.shape[-1] % 8 == 0:
         return _BiasAct.apply(h, bias, ACT_GELU)
     return F.gelu(h + bias)
+
+
+# ---------------------------------------------------------------------------
+# gated activation (SwiGLU / GEGLU): y = act(gate + b_gate) * (up + b_up), x = [gate | up]
+_GATED_ACTS = (ACT_GELU, ACT_GELU_TANH, ACT_SILU)
+
+
+def gated_act_reference(x, bias, act):
+    """The PyTorch composition ``act(gate + b_gate) * (up + b_up)`` with ``gate, up = (x + bias).chunk(2, -1)``:
+    the path for CPU tensors, ``APEX_FORCE_REFERENCE=1``, ``F % 8 != 0`` and float64, and the
+    formulation the CPU tests hold to the float64 bound. 16-bit inputs are computed in fp32 and rounded
+    once, as the kernels do."""
+    if act not in _GATED_ACTS:
+        raise ValueError(f"gated_act: act must be ACT_SILU, ACT_GELU or ACT_GELU_TANH, got {act!r}")
+    if x.shape[-1] % 2:
+        raise ValueError(f"gated_act: the last dimension must be even, got {x.shape[-1]}")
+    ct = torch.float32 if x.dtype in (torch.float16, torch.bfloat16) else x.dtype
+    h = x.to(ct)
+    if bias is not None:
+        h = h + bias.to(ct)
+    gate, up = h.chunk(2, -1)
+    return (_act_ref(gate, act) * up).to(x.dtype)
+
+
+class _GatedAct(torch.autograd.Function):
+    """One HIP kernel each way (csrc/fused_ops.hip glu_fwd / glu_bwd). Only x and the bias are saved:
+    act(gate) is recomputed in the backward, which writes dx = [dgate | dup] directly and takes the
+    bias gradient from the same pass (fp32 partial rows, deterministic reduce)."""
+
+    @staticmethod
+    def forward(ctx, x, b, act):
+        C = _ext.require()
+        x2 = _2d(x).contiguous()
+        if x2.data_ptr() % 16:  # the kernels read 16-byte vectors
+            x2 = x2.clone()
+        bc = b.contiguous() if b is not None else None
+        if bc is not None and bc.data_ptr() % 16:
+            bc = bc.clone()
+        y = C.glu_fwd(x2, bc, act)
+        ctx.save_for_backward(x2, bc)
+        ctx.act = act
+        ctx.xshape = x.shape
+        return y.view(*x.shape[:-1], x.shape[-1] // 2)
+
+    @staticmethod
+    def backward(ctx, dy):
+        C = _ext.require()
+        x2, b = ctx.saved_tensors
+        need_db = b is not None and ctx.needs_input_grad[1]
+        dy2 = _2d(dy).contiguous()
+        if dy2.data_ptr() % 16:
+            dy2 = dy2.clone()
+        dx, db = C.glu_bwd(dy2, x2, b, ctx.act, need_db)
+        return dx.view(ctx.xshape), (db if need_db else None), None
+
+
+def gated_act(x, bias=None, act=ACT_SILU):
+    """``act(gate + b_gate) * (up + b_up)`` for x ``[..., 2F]`` = ``[gate | up]`` (Megatron's ``chunk(2, -1)``
+    order) and an optional bias ``[2F]`` in x's dtype or fp32; returns ``[..., F]``. ``act``: ACT_SILU
+    (SwiGLU), ACT_GELU or ACT_GELU_TANH (GEGLU). x is never modified."""
+    if act not in _GATED_ACTS:
+        raise ValueError(f"gated_act: act must be ACT_SILU, ACT_GELU or ACT_GELU_TANH, got {act!r}")
+    if x.shape[-1] % 2:
+        raise ValueError(f"gated_act: the last dimension must be even, got {x.shape[-1]}")
+    if bias is not None and bias.shape != (x.shape[-1],):
+        raise ValueError(f"gated_act: bias must be [{x.shape[-1]}], got {tuple(bias.shape)}")
+    if (_native(x) and x.shape[-1] % 16 == 0 and x.dtype in (torch.float32, torch.float16, torch.bfloat16)
+            and (bias is None or (bias.device == x.device and bias.dtype in (x.dtype, torch.float32)))):
+        return _GatedAct.apply(x, bias, act)
+    return gated_act_reference(x, bias, act)
+
+
+def bias_swiglu(x, bias=None):
+    """SwiGLU: ``silu(gate + b_gate) * (up + b_up)``, x = ``[gate | up]``."""
+    return gated_act(x, bias, ACT_SILU)
+
+
+def bias_geglu(x, bias=None, approximate="none"):
+    """GEGLU: ``gelu(gate + b_gate) * (up + b_up)``, x = ``[gate | up]``; approximate "none" (erf) or "tanh"."""
+    if approximate not in ("none", "tanh"):
+        raise ValueError(f"bias_geglu: approximate must be 'none' or 'tanh', got {approximate!r}")
+    return gated_act(x, bias, ACT_GELU if approximate == "none" else ACT_GELU_TANH)
 
 
 # ---------------------------------------------------------------------------

@@ -26,6 +26,8 @@ def main():
     ap.add_argument("--size", default="1.5b", choices=["1.5b", "medium", "tiny"])
     ap.add_argument("--rope", action="store_true",
                     help="rotary position embeddings (fused RoPE on packed QKV) instead of the learned wpe")
+    ap.add_argument("--activation", default="gelu", choices=["gelu", "swiglu", "geglu"],
+                    help="MLP activation; swiglu / geglu: the gated MLP (fused gated-activation kernel)")
     args = ap.parse_args()
 
     from apex.utils.bench import emit, finish, init_distributed, instrumented_steps
@@ -45,6 +47,7 @@ def main():
     cfg = {"1.5b": GPTConfig.gpt2_1_5b, "medium": GPTConfig.gpt2_medium, "tiny": GPTConfig.tiny}[args.size]()
     if args.rope:
         cfg.position_embedding_type = "rope"
+    cfg.activation = args.activation
     model = GPTModel(cfg).to(env.device)
     opt = FusedAdam(param_groups(model, 0.1), lr=1.5e-4, betas=(0.9, 0.95), eps=1e-8)
     model, opt = amp.initialize(model, opt, opt_level="O2", cast_model_type=torch.bfloat16, verbosity=0)
@@ -68,7 +71,7 @@ def main():
          config={"model": f"GPT-2 {args.size} ({cfg.n_layer}L, H{cfg.n_embd}, {cfg.n_head} heads, "
                           f"{nparams / 1e9:.2f}B params)",
                  "global_batch": args.batch * env.world, "seq_len": args.seq, "parallelism": f"dp{env.world}",
-                 "position_embedding": cfg.position_embedding_type},
+                 "position_embedding": cfg.position_embedding_type, "activation": cfg.activation},
          extra=dict(extra, final_loss=round(float(loss), 4)))
     finish(env)
 

@@ -648,6 +648,51 @@ std::vector<Tensor> k_bias_act_bwd(Tensor dy, Tensor x, const c10::optional<Tens
   return {dx, db};
 }
 
+// gated activation: x2d [rows, 2F] = [gate | up], bias [2F] (x's dtype or fp32) or None -> y [rows, F]
+int64_t glu_check(const Tensor& x, const c10::optional<Tensor>& b, const char* what) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() && x.size(1) % 2 == 0, what,
+              ": x must be a contiguous [rows, 2F] device tensor");
+  TORCH_CHECK(x.size(1) / 2 < (int64_t)1 << 30, what, ": F too large");
+  if (b.has_value() && b->defined())
+    TORCH_CHECK(b->is_cuda() && b->device() == x.device() && b->is_contiguous() && b->numel() == x.size(1) &&
+                    (b->scalar_type() == x.scalar_type() || b->scalar_type() == at::kFloat),
+                what, ": bias must be a contiguous [2F] tensor on x's device, in x's dtype or fp32");
+  return x.size(1) / 2;
+}
+
+Tensor k_glu_fwd(Tensor x, const c10::optional<Tensor>& b, int64_t act) {
+  const int64_t F = glu_check(x, b, "glu_fwd"), rows = x.size(0);
+  Tensor y = at::empty({rows, F}, x.options());
+  const int bdt = b.has_value() && b->defined() ? dt_code(b->scalar_type()) : dt_code(x.scalar_type());
+  check(apex::glu_fwd(x.data_ptr(), opt_vptr(b), y.data_ptr(), rows, (int)F, (int)act, dt_code(x.scalar_type()),
+                      bdt, cur_stream()),
+        "glu_fwd");
+  return y;
+}
+
+std::tuple<Tensor, c10::optional<Tensor>> k_glu_bwd(Tensor dy, Tensor x, const c10::optional<Tensor>& b, int64_t act,
+                                                    bool need_dbias) {
+  const int64_t F = glu_check(x, b, "glu_bwd"), rows = x.size(0);
+  TORCH_CHECK(dy.is_cuda() && dy.device() == x.device() && dy.dim() == 2 && dy.size(0) == rows && dy.size(1) == F &&
+                  dy.scalar_type() == x.scalar_type(),
+              "glu_bwd: dy must be [rows, F] in x's dtype on x's device");
+  Tensor dyc = dy.contiguous();
+  Tensor dx = at::empty_like(x);
+  const bool hb = need_dbias && b.has_value() && b->defined();
+  Tensor db, ws;
+  if (hb) {
+    db = at::empty_like(*b);
+    ws = at::empty({apex::colsum_parts(rows) * 2 * F}, x.options().dtype(at::kFloat));
+    if (rows == 0) db.zero_();
+  }
+  const int bdt = b.has_value() && b->defined() ? dt_code(b->scalar_type()) : dt_code(x.scalar_type());
+  check(apex::glu_bwd(dyc.data_ptr(), x.data_ptr(), opt_vptr(b), dx.data_ptr(), hb ? db.data_ptr() : nullptr,
+                      hb ? ws.data_ptr<float>() : nullptr, rows, (int)F, (int)act, dt_code(x.scalar_type()), bdt,
+                      cur_stream()),
+        "glu_bwd");
+  return {dx, hb ? c10::optional<Tensor>(db) : c10::nullopt};
+}
+
 Tensor k_bda_fwd(Tensor x, const c10::optional<Tensor>& b, Tensor res, double p, int64_t seed,
                  int64_t offset) {
   TORCH_CHECK(x.is_contiguous() && res.is_contiguous() && x.sizes() == res.sizes(), "bias_dropout_add: shapes");
@@ -1802,6 +1847,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("cu_seqlens") = py::none(), py::arg("rot_heads") = -1, py::arg("backward") = false);
   m.def("bias_act_fwd", &k_bias_act_fwd);
   m.def("bias_act_bwd", &k_bias_act_bwd);
+  m.def("glu_fwd", &k_glu_fwd, py::arg("x"), py::arg("bias"), py::arg("act"));
+  m.def("glu_bwd", &k_glu_bwd, py::arg("dy"), py::arg("x"), py::arg("bias"), py::arg("act"), py::arg("need_dbias"));
   m.def("bias_dropout_add_fwd", &k_bda_fwd);
   m.def("bias_dropout_add_bwd", &k_bda_bwd, py::arg("dy"), py::arg("p"), py::arg("seed"), py::arg("offset"),
         py::arg("bias_like"), py::arg("dbias_out") = py::none());

@@ -2,6 +2,8 @@
 // with the bias gradient folded into the backward pass.
 //
 //   bias_act      y = act(x + b)                         bwd: dx = dy*act'(x+b), db = colsum(dx)
+//   glu           y = act(g + b_g) * (u + b_u)           bwd: dx = [dy*v*act'(a) | dy*act(a)], db = colsum(dx)
+//                 x = [g | u] ([rows, 2F], read in place)     (SwiGLU / GEGLU; act(a) recomputed)
 //   bias_drop_add y = res + dropout(x + b)               bwd: dres = dy, dx = dy*mask/(1-p), db
 //   bdaln         s = res + dropout(x + b); y = LN(s)     bwd: LN bwd -> ds; dres = ds; dx; db,
 //                                                              dgamma, dbeta
@@ -33,12 +35,23 @@ __device__ __forceinline__ float gelu_tanh_grad(float x) {
   const float t = tanhf(u);
   return 0.5f * (1.f + t) + 0.5f * x * (1.f - t * t) * 0.7978845608028654f * (1.f + 3.f * 0.044715f * x * x);
 }
+// SiLU through sigma = 1 / (1 + e^-x): e^-x overflows to +inf for x < -88.7 and sigma becomes an exact 0,
+// it underflows to 0 for large x and sigma an exact 1, so x * sigma and sigma * (1 + x * (1 - sigma)) are
+// finite for every finite x (the quotient form x e^-x / (1 + e^-x)^2 is inf / inf there). expf, not
+// __expf: for x well below 0 sigma is e^x itself and the fast exp's relative error grows with |x|.
+__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
+__device__ __forceinline__ float silu(float x) { return x * sigmoid_f(x); }
+__device__ __forceinline__ float silu_grad(float x) {
+  const float sg = sigmoid_f(x);
+  return sg * (1.f + x * (1.f - sg));
+}
 
 template <int ACT>
 __device__ __forceinline__ float act_f(float x) {
   if (ACT == 0) return gelu_erf(x);
   if (ACT == 1) return gelu_tanh(x);
   if (ACT == 2) return fmaxf(x, 0.f);
+  if (ACT == 4) return silu(x);
   return x;  // identity
 }
 template <int ACT>
@@ -46,6 +59,7 @@ __device__ __forceinline__ float act_g(float x) {
   if (ACT == 0) return gelu_erf_grad(x);
   if (ACT == 1) return gelu_tanh_grad(x);
   if (ACT == 2) return x > 0.f ? 1.f : 0.f;
+  if (ACT == 4) return silu_grad(x);
   return 1.f;
 }
 
@@ -124,6 +138,80 @@ __global__ void __launch_bounds__(kEwBlock) bias_act_bwd_kernel(const T* __restr
     store_f<T, 8>(dx + r * g.cols + c, d);
   }
   if (part) store_f<float, 8>(part + (int64_t)blockIdx.y * g.cols + c, acc);
+}
+
+// ------------------------- gated activation (SwiGLU / GEGLU) ----------------
+// x [rows, 2F] = [gate | up] (Megatron's chunk(2, -1) order), b [2F] or null, y [rows, F]; g.cols = F.
+// A thread owns 8 consecutive columns c of F and reads the gate at c and the up half at F + c of the
+// same row, in place (no split copy).
+template <typename T, typename W, int ACT>
+__global__ void __launch_bounds__(kEwBlock) glu_fwd_kernel(const T* __restrict__ x, const W* __restrict__ b,
+                                                          T* __restrict__ y, ColGeom g) {
+  const int c = (blockIdx.x * kEwBlock + threadIdx.x) * 8;
+  if (c >= g.cols) return;
+  float bg[8], bu[8];
+  if (b) {
+    load_f<W, 8>(b + c, bg);
+    load_f<W, 8>(b + g.cols + c, bu);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) bg[k] = bu[k] = 0.f;
+  }
+  const int64_t r0 = (int64_t)blockIdx.y * g.rpb;
+  const int64_t r1 = min(r0 + g.rpb, g.rows);
+  for (int64_t r = r0; r < r1; ++r) {
+    const T* xr = x + r * 2 * g.cols + c;
+    float a[8], v[8];
+    load_f<T, 8>(xr, a);
+    load_f<T, 8>(xr + g.cols, v);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = act_f<ACT>(a[k] + bg[k]) * (v[k] + bu[k]);
+    store_f<T, 8>(y + r * g.cols + c, v);
+  }
+}
+
+// dx [rows, 2F] = [dgate | dup] written in place of a cat; part: fp32 partial rows [parts][2F] of the
+// unrounded dx (null: no bias gradient), reduced by launch_partial_colsum.
+template <typename T, typename W, int ACT>
+__global__ void __launch_bounds__(kEwBlock) glu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
+                                                          const W* __restrict__ b, T* __restrict__ dx,
+                                                          float* __restrict__ part, ColGeom g) {
+  const int c = (blockIdx.x * kEwBlock + threadIdx.x) * 8;
+  if (c >= g.cols) return;
+  float bg[8], bu[8], accg[8], accu[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) accg[k] = accu[k] = 0.f;
+  if (b) {
+    load_f<W, 8>(b + c, bg);
+    load_f<W, 8>(b + g.cols + c, bu);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) bg[k] = bu[k] = 0.f;
+  }
+  const int64_t r0 = (int64_t)blockIdx.y * g.rpb;
+  const int64_t r1 = min(r0 + g.rpb, g.rows);
+  for (int64_t r = r0; r < r1; ++r) {
+    const int64_t e = r * 2 * g.cols + c;
+    float a[8], v[8], d[8];
+    load_f<T, 8>(x + e, a);
+    load_f<T, 8>(x + e + g.cols, v);
+    load_f<T, 8>(dy + r * g.cols + c, d);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float ak = a[k] + bg[k];
+      a[k] = d[k] * (v[k] + bu[k]) * act_g<ACT>(ak);  // dgate
+      v[k] = d[k] * act_f<ACT>(ak);                    // dup
+      accg[k] += a[k];
+      accu[k] += v[k];
+    }
+    store_f<T, 8>(dx + e, a);
+    store_f<T, 8>(dx + e + g.cols, v);
+  }
+  if (part) {
+    float* pr = part + (int64_t)blockIdx.y * 2 * g.cols + c;
+    store_f<float, 8>(pr, accg);
+    store_f<float, 8>(pr + g.cols, accu);
+  }
 }
 
 // ----------------------------- bias + dropout + residual ---------------------
@@ -844,6 +932,15 @@ __global__ void __launch_bounds__(kEwBlock) embed_segsum_kernel(const T* __restr
     case 1: { constexpr int ACT = 1; __VA_ARGS__; } break;  \
     case 2: { constexpr int ACT = 2; __VA_ARGS__; } break;  \
     case 3: { constexpr int ACT = 3; __VA_ARGS__; } break;  \
+    case 4: { constexpr int ACT = 4; __VA_ARGS__; } break;  \
+    default: return -1;                                     \
+  }
+// the gated kernels' activations: erf-GELU, tanh-GELU (GEGLU) and SiLU (SwiGLU)
+#define GLU_ACT(A, ACT, ...)                                \
+  switch (A) {                                              \
+    case 0: { constexpr int ACT = 0; __VA_ARGS__; } break;  \
+    case 1: { constexpr int ACT = 1; __VA_ARGS__; } break;  \
+    case 4: { constexpr int ACT = 4; __VA_ARGS__; } break;  \
     default: return -1;                                     \
   }
 
@@ -891,6 +988,36 @@ int bias_act_bwd(const void* dy, const void* x, const void* b, void* dx, void* d
                        (const T*)x, (const W*)b, (T*)dx, db ? ws : nullptr, g);
     if (db)
       launch_partial_colsum<W>(ws, parts, (int64_t)cols, cols, (W*)db, s);
+  })));
+  return (int)hipGetLastError();
+}
+
+int glu_fwd(const void* x, const void* b, void* y, int64_t rows, int F, int act, int xdt, int bdt,
+            hipStream_t s) {
+  if (rows == 0 || F == 0) return 0;
+  if (F % 8) return -2;
+  ColGeom g = col_geom(rows, F, 512);
+  dim3 grid((F / 8 + kEwBlock - 1) / kEwBlock, (unsigned)((rows + g.rpb - 1) / g.rpb));
+  if (!b) bdt = xdt;
+  APEX_DISPATCH_T(xdt, T, APEX_DISPATCH_T(bdt, W, GLU_ACT(act, ACT,
+      hipLaunchKernelGGL((glu_fwd_kernel<T, W, ACT>), grid, dim3(kEwBlock), 0, s, (const T*)x, (const W*)b,
+                         (T*)y, g))));
+  return (int)hipGetLastError();
+}
+
+int glu_bwd(const void* dy, const void* x, const void* b, void* dx, void* db, float* ws, int64_t rows, int F,
+            int act, int xdt, int bdt, hipStream_t s) {
+  if (rows == 0 || F == 0) return 0;
+  if (F % 8) return -2;
+  ColGeom g = col_geom(rows, F, 512);
+  const int parts = (int)((rows + g.rpb - 1) / g.rpb);
+  dim3 grid((F / 8 + kEwBlock - 1) / kEwBlock, parts);
+  if (!b) bdt = xdt;
+  APEX_DISPATCH_T(xdt, T, APEX_DISPATCH_T(bdt, W, GLU_ACT(act, ACT, {
+    hipLaunchKernelGGL((glu_bwd_kernel<T, W, ACT>), grid, dim3(kEwBlock), 0, s, (const T*)dy, (const T*)x,
+                       (const W*)b, (T*)dx, db ? ws : nullptr, g);
+    if (db)
+      launch_partial_colsum<W>(ws, parts, 2 * (int64_t)F, 2 * F, (W*)db, s);
   })));
   return (int)hipGetLastError();
 }

@@ -158,12 +158,19 @@ int attn_dropout_mask(uint8_t* out, int64_t BH, int Sq, int Sk, uint64_t seed, u
                       uint32_t thresh, hipStream_t s);
 
 // ----------------------------- fused elementwise ---------------------------
-// act: 0 gelu(erf), 1 gelu(tanh), 2 relu, 3 identity. cols % 8 == 0.
+// act: 0 gelu(erf), 1 gelu(tanh), 2 relu, 3 identity, 4 silu. cols % 8 == 0.
 int bias_act_fwd(const void* x, const void* b, void* y, int64_t rows, int cols, int act, int xdt,
                  int bdt, hipStream_t s);
 // ws: >= colsum_parts(rows) * cols floats
 int bias_act_bwd(const void* dy, const void* x, const void* b, void* dx, void* db, float* ws,
                  int64_t rows, int cols, int act, int xdt, int bdt, hipStream_t s);
+// gated activation y[rows, F] = act(g + b_g) * (u + b_u), x[rows, 2F] = [g | u], b[2F] or null;
+// act: 0 gelu(erf), 1 gelu(tanh), 4 silu. F % 8 == 0 (-2 otherwise).
+int glu_fwd(const void* x, const void* b, void* y, int64_t rows, int F, int act, int xdt, int bdt,
+            hipStream_t s);
+// dx[rows, 2F] = [dgate | dup]; db[2F] in the bias dtype (null: skipped); ws: >= colsum_parts(rows) * 2F floats
+int glu_bwd(const void* dy, const void* x, const void* b, void* dx, void* db, float* ws, int64_t rows, int F,
+            int act, int xdt, int bdt, hipStream_t s);
 int bias_dropout_add_fwd(const void* x, const void* b, const void* res, void* y, int64_t rows, int cols,
                          uint64_t seed, uint64_t offset, uint32_t thresh, float scale, int xdt, int bdt,
                          hipStream_t s);
