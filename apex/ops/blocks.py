@@ -462,7 +462,8 @@ def attention_sublayer(x, wqkv, bqkv, wo, bo, gamma, beta, heads, p_attn=0.0, p_
     not apply (caller falls back to the op-by-op composition)."""
     E = x.shape[-1]
     d = E // heads
-    if not (_ok(x, E) and d in (32, 64, 128, 256) and gamma is not None and beta is not None):
+    if not (_ok(x, E) and d in (32, 64, 128, 256) and gamma is not None and beta is not None and
+            (bo is None or bo.dtype == gamma.dtype)):   # the bdaln kernel reads the bias through gamma's type
         return None
     p_attn = p_attn if training else 0.0
     p_hidden = p_hidden if training else 0.0
@@ -472,6 +473,7 @@ def attention_sublayer(x, wqkv, bqkv, wo, bo, gamma, beta, heads, p_attn=0.0, p_
 
 def ffn_sublayer(x, w1, b1, w2, b2, gamma, beta, p=0.0, eps=1e-12, act=ACT_GELU, training=True):
     """LN(x + dropout(act(x W1^T + b1) W2^T + b2)); None when the fused path does not apply."""
-    if not (_ok(x, x.shape[-1], w1.shape[0]) and gamma is not None and beta is not None):
+    if not (_ok(x, x.shape[-1], w1.shape[0]) and gamma is not None and beta is not None and
+            (b2 is None or b2.dtype == gamma.dtype)):   # the bdaln kernel reads the bias through gamma's type
         return None
     return _FFNSublayer.apply(x, w1, b1, w2, b2, gamma, beta, float(p if training else 0.0), float(eps), int(act))

@@ -564,6 +564,29 @@ def bert_embeddings(input_ids, token_type_ids, word, position, token_type, gamma
 
 
 # ---------------------------------------------------------------------------
+def _bdaln_bias_ok(bias, gamma):
+    """The bdaln kernels read the bias through gamma's type. A bias in gamma's dtype goes in as it is; a
+    16-bit bias next to fp32 LayerNorm parameters (the usual mixed-precision layout) goes in as an exact
+    fp32 copy and its gradient is cast back (_bdaln_bias, _bdaln_dbias); any other pair would lose bits of
+    the bias on the way in and takes the composition."""
+    return bias is None or gamma is None or bias.dtype == gamma.dtype or \
+        (gamma.dtype == torch.float32 and bias.dtype in (torch.float16, torch.bfloat16))
+
+
+def _bdaln_bias(b, gamma):
+    return b if b is None or b.dtype == gamma.dtype else b.to(gamma.dtype)
+
+
+def _bdaln_dbias(db, pb):
+    """The bias gradient in the bias's own dtype (the kernel writes gamma's)."""
+    return db if pb is None or db is None or db.dtype == pb.dtype else db.to(pb.dtype)
+
+
+def _bdaln_dbias_out(pb, gamma):
+    """The bias's DDP bucket slot, where the kernel can write it directly."""
+    return _gt(pb) if pb is not None and pb.dtype == gamma.dtype else None
+
+
 class _DenseBDALN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, res, gamma, beta, p, eps):
@@ -574,8 +597,8 @@ class _DenseBDALN(torch.autograd.Function):
         ctx.f8 = G.fp8_state()
         t = G.linear(x2, w, f8=ctx.f8)
         seed, off = _seed(x.device) if p > 0 else (0, 0)
-        y, s, mean, rstd = C.bdaln_fwd(t, b, _2d(res).contiguous(), gamma, beta, float(eps), float(p),
-                                       seed, off)
+        y, s, mean, rstd = C.bdaln_fwd(t, _bdaln_bias(b, gamma), _2d(res).contiguous(), gamma, beta, float(eps),
+                                       float(p), seed, off)
         ctx.save_for_backward(x2, w, s, gamma, mean, rstd)
         ctx.cfg = (p, seed, off, b is not None)
         ctx.params = (w, b, gamma, beta)
@@ -589,7 +612,8 @@ class _DenseBDALN(torch.autograd.Function):
         pw, pb, pg, pbeta = ctx.params
         dres, dt, dg, dbeta, db = C.bdaln_bwd(_2d(dy), s, gamma, mean, rstd, float(p), seed, off, has_b,
                                               dgamma_out=_gt(pg), dbeta_out=_gt(pbeta),
-                                              dbias_out=_gt(pb) if has_b else None)
+                                              dbias_out=_bdaln_dbias_out(pb, gamma) if has_b else None)
+        db = _bdaln_dbias(db, pb)
         from . import gemm as G
 
         dx = G.dgrad(dt, w, f8=ctx.f8).view(*dy.shape[:-1], w.shape[1]) if ctx.needs_input_grad[0] else None
@@ -601,7 +625,7 @@ def dense_bias_dropout_add_ln(x, weight, bias, residual, gamma, beta, p=0.0, eps
     """LayerNorm(residual + dropout(x @ W^T + b)) — BERT's post-LN sublayer output."""
     p = p if training else 0.0
     if _native(x) and _ext.require().bdaln_supported(weight.shape[0]) and gamma is not None and \
-            beta is not None:
+            beta is not None and _bdaln_bias_ok(bias, gamma):
         return _DenseBDALN.apply(x, weight, bias, residual, gamma, beta, float(p), float(eps))
     t = F.linear(x, weight, bias)
     s = residual + F.dropout(t, p, True) if p > 0 else residual + t
@@ -619,8 +643,8 @@ class _BDAPreLN(torch.autograd.Function):
     def forward(ctx, x, b, res, gamma, beta, p, eps):
         C = _ext.require()
         seed, off = _seed(x.device) if p > 0 else (0, 0)
-        y, s, mean, rstd = C.bdaln_fwd(_2d(x).contiguous(), b, _2d(res).contiguous(), gamma, beta, float(eps),
-                                       float(p), seed, off)
+        y, s, mean, rstd = C.bdaln_fwd(_2d(x).contiguous(), _bdaln_bias(b, gamma), _2d(res).contiguous(), gamma, beta,
+                                       float(eps), float(p), seed, off)
         ctx.save_for_backward(s, gamma, mean, rstd)
         ctx.cfg = (p, seed, off, b is not None)
         ctx.params = (b, gamma, beta)
@@ -637,8 +661,9 @@ class _BDAPreLN(torch.autograd.Function):
             dy = torch.zeros_like(s)
         dres, dx, dg, dbeta, db = C.bdaln_bwd(_2d(dy), s, gamma, mean, rstd, float(p), seed, off, has_b,
                                               dgamma_out=_gt(pg), dbeta_out=_gt(pbeta),
-                                              dbias_out=_gt(pb) if has_b else None,
+                                              dbias_out=_bdaln_dbias_out(pb, gamma) if has_b else None,
                                               ds_extra=_2d(ds) if ds is not None else None)
+        db = _bdaln_dbias(db, pb)
         return (dx.view(ctx.shape), (db if has_b else None), dres.view(ctx.shape), dg, dbeta, None, None)
 
 
@@ -647,6 +672,7 @@ def bias_dropout_add_ln(x, bias, residual, gamma, beta, p=0.0, eps=1e-5, trainin
     with the next LayerNorm (GPT-2 / Megatron layer boundaries)."""
     p = p if training else 0.0
     if _native(x) and x.shape == residual.shape and gamma is not None and beta is not None and \
+            _bdaln_bias_ok(bias, gamma) and \
             (_ext.require().bdaln_supported(x.shape[-1]) or _ext.require().bdaln_wide_supported(x.shape[-1])):
         return _BDAPreLN.apply(x, bias, residual, gamma, beta, float(p), float(eps))
     t = x + bias if bias is not None else x

@@ -3,6 +3,7 @@
 #include <ATen/hip/HIPContext.h>
 #include <torch/extension.h>
 
+#include <cstdint>
 #include <limits>
 #include <vector>
 
@@ -622,9 +623,40 @@ Tensor out_or_empty(const c10::optional<Tensor>& out, at::IntArrayRef sizes, con
   return at::empty(sizes, opt);
 }
 
+// The fused kernels read their operands through raw pointers, so every operand is checked here, before
+// any launch. x: the [rows, cols] activations that set the device, the dtype and the geometry.
+void fused_x(const Tensor& x, const char* op) {
+  TORCH_CHECK(x.defined() && x.is_cuda() && x.is_contiguous(), op, ": the activations must be a contiguous device tensor");
+  TORCH_CHECK(cols_of(x) <= (int64_t)INT32_MAX, op, ": too many columns");
+}
+// a contiguous tensor on x's device
+void fused_dev(const Tensor& t, const Tensor& x, const char* op, const char* name) {
+  TORCH_CHECK(t.defined() && t.is_cuda() && t.device() == x.device() && t.is_contiguous(), op, ": ", name,
+              " must be a contiguous tensor on the activations' device");
+}
+// ... with the dtype and the element count of `like` (an activation next to x, beta next to gamma)
+void fused_like(const Tensor& t, const Tensor& like, const char* op, const char* name) {
+  fused_dev(t, like, op, name);
+  TORCH_CHECK(t.scalar_type() == like.scalar_type() && t.numel() == like.numel(), op, ": ", name,
+              " must have the dtype and the number of elements of the tensor it goes with");
+}
+// a per-column vector (bias, gamma, beta): cols elements in a dtype the kernels dispatch on
+void fused_vec(const Tensor& t, const Tensor& x, int64_t cols, const char* op, const char* name) {
+  fused_dev(t, x, op, name);
+  TORCH_CHECK(t.numel() == cols, op, ": ", name, " must have one element per column");
+  (void)dt_code(t.scalar_type());
+}
+// fp32 per-row statistics (mean, rstd)
+void fused_stat(const Tensor& t, const Tensor& x, int64_t rows, const char* op, const char* name) {
+  fused_dev(t, x, op, name);
+  TORCH_CHECK(t.scalar_type() == at::kFloat && t.numel() == rows, op, ": ", name, " must be fp32 with one element per row");
+}
+bool has(const c10::optional<Tensor>& t) { return t.has_value() && t->defined(); }
+
 Tensor k_bias_act_fwd(Tensor x, const c10::optional<Tensor>& b, int64_t act) {
-  TORCH_CHECK(x.is_contiguous(), "bias_act: x must be contiguous");
+  fused_x(x, "bias_act_fwd");
   const int64_t cols = cols_of(x), rows = x.numel() / std::max<int64_t>(cols, 1);
+  if (has(b)) fused_vec(*b, x, cols, "bias_act_fwd", "bias");
   Tensor y = at::empty_like(x);
   const int bdt = b.has_value() && b->defined() ? dt_code(b->scalar_type()) : dt_code(x.scalar_type());
   check(apex::bias_act_fwd(x.data_ptr(), opt_vptr(b), y.data_ptr(), rows, (int)cols, (int)act,
@@ -634,11 +666,15 @@ Tensor k_bias_act_fwd(Tensor x, const c10::optional<Tensor>& b, int64_t act) {
 }
 
 std::vector<Tensor> k_bias_act_bwd(Tensor dy, Tensor x, const c10::optional<Tensor>& b, int64_t act) {
+  fused_x(x, "bias_act_bwd");
   const int64_t cols = cols_of(x), rows = x.numel() / std::max<int64_t>(cols, 1);
   Tensor dyc = dy.contiguous();
+  fused_like(dyc, x, "bias_act_bwd", "dy");
   Tensor dx = at::empty_like(x);
   const bool hb = b.has_value() && b->defined();
+  if (hb) fused_vec(*b, x, cols, "bias_act_bwd", "bias");
   Tensor db = hb ? at::empty_like(*b) : Tensor();
+  if (hb && rows == 0) db.zero_();  // no row: the launcher returns before any kernel
   Tensor ws = hb ? at::empty({apex::colsum_parts(rows) * cols}, x.options().dtype(at::kFloat)) : Tensor();
   const int bdt = hb ? dt_code(b->scalar_type()) : dt_code(x.scalar_type());
   check(apex::bias_act_bwd(dyc.data_ptr(), x.data_ptr(), opt_vptr(b), dx.data_ptr(),
@@ -695,8 +731,11 @@ std::tuple<Tensor, c10::optional<Tensor>> k_glu_bwd(Tensor dy, Tensor x, const c
 
 Tensor k_bda_fwd(Tensor x, const c10::optional<Tensor>& b, Tensor res, double p, int64_t seed,
                  int64_t offset) {
-  TORCH_CHECK(x.is_contiguous() && res.is_contiguous() && x.sizes() == res.sizes(), "bias_dropout_add: shapes");
+  fused_x(x, "bias_dropout_add_fwd");
+  fused_like(res, x, "bias_dropout_add_fwd", "res");
+  TORCH_CHECK(x.sizes() == res.sizes(), "bias_dropout_add: shapes");
   const int64_t cols = cols_of(x), rows = x.numel() / std::max<int64_t>(cols, 1);
+  if (has(b)) fused_vec(*b, x, cols, "bias_dropout_add_fwd", "bias");
   Tensor y = at::empty_like(x);
   auto dp = drop_params(p);
   const int bdt = b.has_value() && b->defined() ? dt_code(b->scalar_type()) : dt_code(x.scalar_type());
@@ -710,10 +749,16 @@ Tensor k_bda_fwd(Tensor x, const c10::optional<Tensor>& b, Tensor res, double p,
 std::vector<Tensor> k_bda_bwd(Tensor dy, double p, int64_t seed, int64_t offset,
                               const c10::optional<Tensor>& bias_like, const c10::optional<Tensor>& dbias_out) {
   Tensor dyc = dy.contiguous();
+  fused_x(dyc, "bias_dropout_add_bwd");
   const int64_t cols = cols_of(dyc), rows = dyc.numel() / std::max<int64_t>(cols, 1);
   Tensor dx = at::empty_like(dyc);
   const bool hb = bias_like.has_value() && bias_like->defined();
+  // (bias_like is not read: it gives the bias gradient's shape, dtype and device)
+  if (hb)
+    TORCH_CHECK(bias_like->numel() == cols && bias_like->device() == dyc.device(),
+                "bias_dropout_add_bwd: the bias must have one element per column, on dy's device");
   Tensor db = hb ? out_or_empty(dbias_out, bias_like->sizes(), bias_like->options(), "bias_dropout_add_bwd") : Tensor();
+  if (hb && rows == 0) db.zero_();
   Tensor ws = hb ? at::empty({apex::colsum_parts(rows) * cols}, dyc.options().dtype(at::kFloat)) : Tensor();
   auto dp = drop_params(p);
   check(apex::bias_dropout_add_bwd(dyc.data_ptr(), dx.data_ptr(), hb ? db.data_ptr() : nullptr,
@@ -727,8 +772,10 @@ std::vector<Tensor> k_bda_bwd(Tensor dy, double p, int64_t seed, int64_t offset,
 
 Tensor k_colsum(Tensor x, at::ScalarType out_dtype, const c10::optional<Tensor>& out_opt) {
   Tensor xc = x.contiguous();
+  fused_x(xc, "colsum");
   const int64_t cols = cols_of(xc), rows = xc.numel() / std::max<int64_t>(cols, 1);
   Tensor out = out_or_empty(out_opt, {cols}, xc.options().dtype(out_dtype), "colsum");
+  if (rows == 0) out.zero_();
   Tensor ws = at::empty({apex::colsum_parts(rows) * cols}, xc.options().dtype(at::kFloat));
   check(apex::colsum(xc.data_ptr(), out.data_ptr(), ws.data_ptr<float>(), rows, (int)cols,
                      dt_code(xc.scalar_type()), dt_code(out_dtype), cur_stream()),
@@ -783,8 +830,17 @@ std::vector<Tensor> k_bdaln_fwd(Tensor x, const c10::optional<Tensor>& b, Tensor
                                 Tensor beta, double eps, double p, int64_t seed, int64_t offset, bool store_s,
                                 const c10::optional<Tensor>& q8_out, const c10::optional<Tensor>& q8_scale,
                                 const c10::optional<Tensor>& q8_amax, int64_t q8_fmt, bool s_cond) {
-  TORCH_CHECK(x.is_contiguous() && res.is_contiguous() && x.sizes() == res.sizes(), "bdaln: shapes");
+  fused_x(x, "bdaln_fwd");
+  fused_like(res, x, "bdaln_fwd", "res");
+  TORCH_CHECK(x.sizes() == res.sizes(), "bdaln: shapes");
   const int64_t cols = cols_of(x), rows = x.numel() / std::max<int64_t>(cols, 1);
+  fused_vec(gamma, x, cols, "bdaln_fwd", "gamma");
+  fused_like(beta, gamma, "bdaln_fwd", "beta");
+  if (has(b)) {
+    // the kernel reads the bias through gamma's type
+    fused_vec(*b, x, cols, "bdaln_fwd", "bias");
+    TORCH_CHECK(b->scalar_type() == gamma.scalar_type(), "bdaln_fwd: the bias must have gamma's dtype");
+  }
   Tensor y = at::empty_like(x), s = store_s ? at::empty_like(x) : at::empty({0}, x.options());
   auto fo = x.options().dtype(at::kFloat);
   Tensor mean = at::empty({rows}, fo), rstd = at::empty({rows}, fo);
@@ -808,21 +864,30 @@ std::vector<Tensor> k_bdaln_bwd(Tensor dy, Tensor s, Tensor gamma, Tensor mean, 
   // beta given: `s` is the LN output y of a store_s = false (or s_cond) forward (x-hat = (y - beta) /
   // gamma); s_alt: the s_cond forward's conditionally stored LN input, read instead when gamma has a 0
   Tensor dyc = dy.contiguous();
-  const bool from_y = beta.has_value() && beta->defined();
-  if (from_y)
-    TORCH_CHECK(beta->is_contiguous() && beta->sizes() == gamma.sizes() && beta->scalar_type() == gamma.scalar_type() &&
-                    s.is_contiguous(),
-                "bdaln_bwd: beta like gamma, y contiguous");
+  fused_x(s, "bdaln_bwd");
+  fused_like(dyc, s, "bdaln_bwd", "dy");
   const int64_t cols = cols_of(s), rows = s.numel() / std::max<int64_t>(cols, 1);
+  fused_vec(gamma, s, cols, "bdaln_bwd", "gamma");
+  fused_stat(mean, s, rows, "bdaln_bwd", "mean");
+  fused_stat(rstd, s, rows, "bdaln_bwd", "rstd");
+  const bool from_y = beta.has_value() && beta->defined();
+  if (from_y) fused_like(*beta, gamma, "bdaln_bwd", "beta");
   Tensor dse;
   if (ds_extra.has_value() && ds_extra->defined()) {
     dse = ds_extra->contiguous();
-    TORCH_CHECK(dse.numel() == s.numel() && dse.scalar_type() == s.scalar_type(), "bdaln_bwd: ds_extra like s");
+    fused_like(dse, s, "bdaln_bwd", "ds_extra");
   }
+  const bool use_alt = from_y && has(s_alt) && s_alt->numel() == s.numel();
+  if (use_alt) fused_like(*s_alt, s, "bdaln_bwd", "s_alt");
   Tensor dres = at::empty_like(s), dx = at::empty_like(s);
   Tensor dgamma = out_or_empty(dgamma_out, gamma.sizes(), gamma.options(), "bdaln_bwd dgamma");
   Tensor dbeta = out_or_empty(dbeta_out, gamma.sizes(), gamma.options(), "bdaln_bwd dbeta");
   Tensor dbias = has_bias ? out_or_empty(dbias_out, gamma.sizes(), gamma.options(), "bdaln_bwd dbias") : Tensor();
+  if (rows == 0) {  // no row: the launcher returns before any kernel
+    dgamma.zero_();
+    dbeta.zero_();
+    if (has_bias) dbias.zero_();
+  }
   Tensor ws = at::empty({apex::bdaln_ws_floats(rows, (int)cols)}, s.options().dtype(at::kFloat));
   auto dp = drop_params(p);
   apex::Q8Out q8 = q8_args(q8_out, q8_scale, q8_amax, q8_fmt, dx, "bdaln_bwd");
@@ -837,8 +902,7 @@ std::vector<Tensor> k_bdaln_bwd(Tensor dy, Tensor s, Tensor gamma, Tensor mean, 
                         (int)cols, (uint64_t)seed, (uint64_t)offset, dp.first, dp.second,
                         dt_code(s.scalar_type()), dt_code(gamma.scalar_type()), cur_stream(),
                         q8,
-                        (from_y && s_alt.has_value() && s_alt->defined() && s_alt->numel() == s.numel())
-                            ? s_alt->data_ptr() : nullptr),
+                        use_alt ? s_alt->data_ptr() : nullptr),
         "bdaln_bwd");
   return {dres, dx, dgamma, dbeta, dbias};
 }
@@ -854,13 +918,21 @@ std::vector<Tensor> k_embed_ln_fwd(Tensor ids, const c10::optional<Tensor>& tids
                   Wp.size(1) == Ww.size(1) && Wt.size(1) == Ww.size(1) && Wp.scalar_type() == Ww.scalar_type() &&
                   Wt.scalar_type() == Ww.scalar_type() && Wp.size(0) >= ids.size(1),
               "embed_ln_fwd: tables");
+  fused_x(Ww, "embed_ln_fwd");
+  fused_dev(Wp, Ww, "embed_ln_fwd", "the position table");
+  fused_dev(Wt, Ww, "embed_ln_fwd", "the type table");
+  fused_dev(ids, Ww, "embed_ln_fwd", "ids");
+  TORCH_CHECK(Wp.dim() == 2 && Wt.dim() == 2 && Wt.size(0) >= 1, "embed_ln_fwd: tables");
   const int* tp = nullptr;
   if (tids.has_value() && tids->defined()) {
-    TORCH_CHECK(tids->sizes() == ids.sizes() && tids->is_contiguous() && tids->scalar_type() == at::kInt,
+    TORCH_CHECK(tids->sizes() == ids.sizes() && tids->is_contiguous() && tids->scalar_type() == at::kInt &&
+                    tids->device() == Ww.device(),
                 "embed_ln_fwd: type ids int32 [B, S]");
     tp = tids->data_ptr<int>();
   }
   const int64_t B = ids.size(0), S = ids.size(1), H = Ww.size(1), rows = B * S;
+  fused_vec(gamma, Ww, H, "embed_ln_fwd", "gamma");
+  fused_like(beta, gamma, "embed_ln_fwd", "beta");
   auto xo = Ww.options();
   Tensor y = at::empty({B, S, H}, xo), sv = at::empty({B, S, H}, xo);
   auto fo = xo.dtype(at::kFloat);
@@ -881,17 +953,33 @@ std::vector<Tensor> k_embed_ln_bwd(Tensor dy, Tensor sv, Tensor gamma, Tensor me
                                    const c10::optional<Tensor>& dwt_out, const c10::optional<Tensor>& dgamma_out,
                                    const c10::optional<Tensor>& dbeta_out) {
   Tensor dyc = dy.contiguous();
+  fused_x(sv, "embed_ln_bwd");
+  fused_like(dyc, sv, "embed_ln_bwd", "dy");
   TORCH_CHECK(sv.dim() == 3 && dyc.sizes() == sv.sizes(), "embed_ln_bwd: shapes");
   const int64_t B = sv.size(0), S = sv.size(1), H = sv.size(2);
   TORCH_CHECK(npos >= S && tvocab >= 1 && tvocab <= 2, "embed_ln_bwd: table sizes");
+  fused_vec(gamma, sv, H, "embed_ln_bwd", "gamma");
+  fused_stat(mean, sv, B * S, "embed_ln_bwd", "mean");
+  fused_stat(rstd, sv, B * S, "embed_ln_bwd", "rstd");
   const int* tp = nullptr;
-  if (tids.has_value() && tids->defined()) tp = tids->data_ptr<int>();
+  if (tids.has_value() && tids->defined()) {
+    fused_dev(*tids, sv, "embed_ln_bwd", "type ids");
+    TORCH_CHECK(tids->scalar_type() == at::kInt && tids->numel() == B * S, "embed_ln_bwd: type ids int32 [B, S]");
+    tp = tids->data_ptr<int>();
+  }
   Tensor ds = at::empty_like(sv);
   Tensor dWp = out_or_empty(dwp_out, {npos, H}, sv.options(), "embed_ln_bwd dWp");
   if (npos > S) dWp.view({npos, H}).narrow(0, S, npos - S).zero_();  // positions past S: no gradient
   Tensor dWt = out_or_empty(dwt_out, {tvocab, H}, sv.options(), "embed_ln_bwd dWt");
   Tensor dgamma = out_or_empty(dgamma_out, gamma.sizes(), gamma.options(), "embed_ln_bwd dgamma");
   Tensor dbeta = out_or_empty(dbeta_out, gamma.sizes(), gamma.options(), "embed_ln_bwd dbeta");
+  if (B * S == 0) {  // no token: nothing to launch, every gradient is zero
+    dWp.zero_();
+    dWt.zero_();
+    dgamma.zero_();
+    dbeta.zero_();
+    return {ds, dWp, dWt, dgamma, dbeta};
+  }
   const int nwt = apex::embed_nwt(B);
   auto fo = sv.options().dtype(at::kFloat);
   Tensor part_pos = at::empty({(int64_t)nwt * S * H}, fo);
@@ -911,6 +999,10 @@ Tensor k_embed_segsum(Tensor ds, Tensor sorted_ids, Tensor perm, int64_t vocab, 
   TORCH_CHECK(ds.is_contiguous() && sorted_ids.scalar_type() == at::kInt && perm.scalar_type() == at::kLong &&
                   sorted_ids.is_contiguous() && perm.is_contiguous() && sorted_ids.numel() == perm.numel(),
               "embed_segsum: int32 sorted ids, int64 permutation");
+  fused_x(ds, "embed_segsum");
+  fused_dev(sorted_ids, ds, "embed_segsum", "sorted ids");
+  fused_dev(perm, ds, "embed_segsum", "perm");
+  TORCH_CHECK(ds.dim() >= 1 && ds.size(-1) > 0, "embed_segsum: ds [..., H]");
   const int64_t H = ds.size(-1), R = ds.numel() / H;
   TORCH_CHECK(sorted_ids.numel() == R, "embed_segsum: one id per ds row");
   Tensor dW = out_or_empty(out, {vocab, H}, ds.options(), "embed_segsum");
