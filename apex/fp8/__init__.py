@@ -100,6 +100,13 @@ _FP8_WBATCH = os.environ.get("APEX_FP8_WBATCH", "1")
 _FP8_CODES_ONLY = os.environ.get("APEX_FP8_CODES_ONLY", "1")
 
 
+def _aligned(x):
+    """``x`` contiguous and 16-byte aligned, as the quantisers read it (16-byte vector loads; the
+    binding refuses anything else): ``x`` itself, or a copy of a strided or offset view."""
+    x = x if x.is_contiguous() else x.contiguous()
+    return x if x.data_ptr() % 16 == 0 else x.clone()
+
+
 def _f8_wgrad_splits(R, P, Q, cus=256):
     """Split-K slices for the fp8 weight gradient dW [P, Q] over R tokens. With t 256x256 output
     tiles and s slices the kernel runs ceil(t s / CUs) workgroup rounds of R / s tokens each, so
@@ -249,7 +256,7 @@ class Fp8State:
     def quantize(self, x, key, fmt):
         """Delayed-scaled quantisation of an activation / gradient -> (codes uint8, scale_inv view)."""
         C = _C()
-        x = x if x.is_contiguous() else x.contiguous()
+        x = _aligned(x)
         s = self.slot(key, fmt)
         if s in self._fresh:
             self._fresh.discard(s)
@@ -270,7 +277,7 @@ class Fp8State:
                 return e
         s = self.slot((k, "w"), self._fwd)
         self._fresh.discard(s)
-        w8 = self._current(w.detach().contiguous(), s, self._fwd)
+        w8 = self._current(_aligned(w.detach()), s, self._fwd)
         e = [weakref.ref(w), self.gen, s, w8, None]
         self._wcache[k] = e
         return e
@@ -287,8 +294,8 @@ class Fp8State:
         groups: dict = {}
         for k, (ref, slot, want_t) in prev.items():
             w = ref()
-            if w is None or w.dim() != 2 or not w.is_cuda or not w.is_contiguous():
-                continue
+            if w is None or w.dim() != 2 or not w.is_cuda or not w.is_contiguous() or w.data_ptr() % 16:
+                continue  # (quantised on its own by _weight_entry, from a copy where it has to be)
             if w.dtype not in (torch.bfloat16, torch.float16, torch.float32):
                 continue
             if self.slots.get((k, "w")) != slot:
@@ -313,7 +320,7 @@ class Fp8State:
         """W^T [K, N] codes (same scale as ``weight``), cached for this optimizer step."""
         e = self._weight_entry(w)
         if e[4] is None:
-            e[4] = _C().fp8_quantize_t(w.detach().contiguous(), self._fwd, self._view("scale", e[2]))
+            e[4] = _C().fp8_quantize_t(_aligned(w.detach()), self._fwd, self._view("scale", e[2]))
         return e[4], self._view("scale_inv", e[2])
 
     # ------------------------------------------------------------------ producer-side codes
@@ -395,9 +402,12 @@ class Fp8State:
             return False
         if contraction % 128 or width % 8 or w.dim() != 2:
             return False
-        if bias is not None and bias.dtype != a.dtype:
+        # epilogue operands the kernel reads with 16-byte loads on a's device (the binding refuses others;
+        # a declined GEMM runs in 16 bits, whose wrappers handle such views)
+        if bias is not None and (bias.dtype != a.dtype or bias.device != a.device or bias.data_ptr() % 16):
             return False
-        if aux is not None and (aux.dtype != a.dtype or not aux.is_contiguous()):
+        if aux is not None and (aux.dtype != a.dtype or not aux.is_contiguous() or aux.device != a.device
+                                or aux.data_ptr() % 16):
             return False
         return True
 

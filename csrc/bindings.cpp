@@ -1512,12 +1512,32 @@ std::vector<Tensor> k_gemm(Tensor a, Tensor b, int64_t epi, const c10::optional<
 // FP8 (gemm.hip fp8 path + fp8.hip): a8 [..., K] / b8 [N, K] uint8 e4m3|e5m2 codes, alpha_a /
 // alpha_b fp32 device scalars (the inverse quantisation scales); output in out_dtype
 // ---------------------------------------------------------------------------
-void f8_check_scalar(const Tensor& t, const char* what) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.numel() >= 1, what, " must be an fp32 device scalar");
+// `like`: the operand whose device the launch runs on
+void f8_check_scalar(const Tensor& t, const char* what, const Tensor& like) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.numel() >= 1 && t.device() == like.device(), what,
+              " must be an fp32 scalar on the operand's device");
 }
 
+// an fp32 slot buffer of the scaling state: contiguous, on `like`'s device, n slots or more
+void f8_check_slots(const Tensor& t, const Tensor& like, int64_t n, const char* fn, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device() && t.scalar_type() == at::kFloat && t.is_contiguous() &&
+                  t.numel() >= n,
+              fn, ": ", what, " must be a contiguous fp32 tensor of at least ", n, " slots on ", like.device());
+}
+
+// a quantiser's input: the kernels read 16-bit elements with 16-byte vector loads (fp32: two of them)
+void f8_check_input(const Tensor& x, const char* fn) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous(), fn, ": contiguous device tensor");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf || x.scalar_type() == at::kFloat, fn,
+              ": bf16 / fp16 / fp32 input");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, fn, ": input must be 16-byte aligned");
+}
+
+void f8_check_fmt(int64_t fmt, const char* fn) { TORCH_CHECK(fmt == 0 || fmt == 1, fn, ": fmt 0 (e4m3) or 1 (e5m2)"); }
+
 bool k_gemm_f8_supported(Tensor a, Tensor b) {
-  if (!a.is_cuda() || a.dim() < 2 || b.dim() != 2 || a.scalar_type() != at::kByte || b.scalar_type() != at::kByte)
+  if (!a.is_cuda() || b.device() != a.device() || a.dim() < 2 || b.dim() != 2 || a.scalar_type() != at::kByte ||
+      b.scalar_type() != at::kByte)
     return false;
   if (a.stride(-1) != 1 || b.stride(1) != 1) return false;
   const int64_t K = a.size(-1), N = b.size(0);
@@ -1537,8 +1557,9 @@ std::vector<Tensor> k_gemm_f8(Tensor a, Tensor b, Tensor alpha_a, Tensor alpha_b
   TORCH_CHECK(k_gemm_f8_supported(a, b), "gemm_f8: unsupported operands (uint8 codes, K % 128 == 0, N % 8 == 0, "
               "16-byte aligned, unit inner stride)");
   TORCH_CHECK(out_dtype == at::kBFloat16 || out_dtype == at::kHalf, "gemm_f8: bf16 / fp16 output");
-  f8_check_scalar(alpha_a, "alpha_a");
-  f8_check_scalar(alpha_b, "alpha_b");
+  f8_check_fmt(fmt_a, "gemm_f8");
+  f8_check_scalar(alpha_a, "gemm_f8: alpha_a", a);
+  f8_check_scalar(alpha_b, "gemm_f8: alpha_b", a);
   const int64_t K = a.size(-1), N = b.size(0), M = a.numel() / K;
   std::vector<int64_t> osz(a.sizes().begin(), a.sizes().end());
   osz.back() = N;
@@ -1564,7 +1585,8 @@ std::vector<Tensor> k_gemm_f8(Tensor a, Tensor b, Tensor alpha_a, Tensor alpha_b
   TORCH_CHECK(epi >= 0 && epi <= apex::EPI_MUL && epi != apex::EPI_F32, "gemm_f8: bad epilogue ", epi);
   if (epi == apex::EPI_BIAS || gelu_fwd) {
     TORCH_CHECK(bias.has_value() && bias->defined() && bias->is_contiguous() && bias->numel() == N &&
-                    bias->scalar_type() == out_dtype, "gemm_f8: bias must be a contiguous [N] tensor of out_dtype");
+                    bias->scalar_type() == out_dtype && gemm_operand_ok(a, *bias),
+                "gemm_f8: bias must be a contiguous, 16-byte aligned [N] tensor of out_dtype on a's device");
     g.bias = bias->data_ptr();
   }
   if (gelu_fwd) {
@@ -1573,16 +1595,20 @@ std::vector<Tensor> k_gemm_f8(Tensor a, Tensor b, Tensor alpha_a, Tensor alpha_b
   }
   if (mul || epi == apex::EPI_RESID) {
     TORCH_CHECK(aux.has_value() && aux->defined() && aux->scalar_type() == out_dtype && aux->numel() == M * N &&
-                    aux->is_contiguous(), "gemm_f8: aux must be a contiguous [M, N] tensor of out_dtype");
+                    aux->is_contiguous() && gemm_operand_ok(a, *aux),
+                "gemm_f8: aux must be a contiguous, 16-byte aligned [M, N] tensor of out_dtype on a's device");
     g.aux = aux->data_ptr();
     g.ldaux = N;
   }
   if (mul) {
     part = at::empty({apex::gemm_part_rows((int)M), N}, a.options().dtype(at::kFloat));
     g.part = part.data_ptr<float>();
+    if (bias_grad_dtype.has_value()) dt_code(*bias_grad_dtype);  // (checked before anything is launched)
   }
   g.q8 = q8_args(q8_out, q8_scale, q8_amax, q8_fmt, c, "gemm_f8");
   TORCH_CHECK(!g.q8.y || gelu_fwd || mul, "gemm_f8: q8_out needs a GELU / dGELU / MUL epilogue");
+  // (the codes go out in 8-byte stores at ldc bytes per row)
+  TORCH_CHECK(!g.q8.y || reinterpret_cast<uintptr_t>(g.q8.y) % 16 == 0, "gemm_f8: q8_out must be 16-byte aligned");
   // q8_only: the returned C is allocated but (on the kernels that honour it: bias+GELU+derivative and
   // multiply, full 256x256 tiles) never written — the caller promises that only the codes are read
   TORCH_CHECK(!q8_only || g.q8.y, "gemm_f8: q8_only needs q8_out");
@@ -1602,21 +1628,21 @@ struct F8Opt {
   float* scale_inv = nullptr;
 };
 
-F8Opt f8_opts(const c10::optional<Tensor>& amax, const c10::optional<Tensor>& cur_amax,
+F8Opt f8_opts(const Tensor& x, const c10::optional<Tensor>& amax, const c10::optional<Tensor>& cur_amax,
               const c10::optional<Tensor>& scale_inv, double smax) {
   F8Opt o;
   if (amax.has_value() && amax->defined()) {
-    f8_check_scalar(*amax, "amax");
+    f8_check_scalar(*amax, "amax", x);
     o.amax = amax->data_ptr<float>();
   }
   if (cur_amax.has_value() && cur_amax->defined()) {
-    f8_check_scalar(*cur_amax, "cur_amax");
+    f8_check_scalar(*cur_amax, "cur_amax", x);
     TORCH_CHECK(scale_inv.has_value() && scale_inv->defined() && smax > 0,
                 "fp8 current scaling needs scale_inv and smax > 0");
     o.cur = cur_amax->data_ptr<float>();
   }
   if (scale_inv.has_value() && scale_inv->defined()) {
-    f8_check_scalar(*scale_inv, "scale_inv");
+    f8_check_scalar(*scale_inv, "scale_inv", x);
     o.scale_inv = scale_inv->data_ptr<float>();
   }
   return o;
@@ -1626,9 +1652,10 @@ F8Opt f8_opts(const c10::optional<Tensor>& amax, const c10::optional<Tensor>& cu
 // max|x| already, scale / scale_inv are written (= smax / cur_amax and its inverse)
 Tensor k_fp8_quantize(Tensor x, int64_t fmt, Tensor scale, const c10::optional<Tensor>& amax,
                       const c10::optional<Tensor>& cur_amax, const c10::optional<Tensor>& scale_inv, double smax) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous(), "fp8_quantize: contiguous device tensor");
-  f8_check_scalar(scale, "scale");
-  const F8Opt o = f8_opts(amax, cur_amax, scale_inv, smax);
+  f8_check_input(x, "fp8_quantize");
+  f8_check_fmt(fmt, "fp8_quantize");
+  f8_check_scalar(scale, "scale", x);
+  const F8Opt o = f8_opts(x, amax, cur_amax, scale_inv, smax);
   Tensor y = at::empty(x.sizes(), x.options().dtype(at::kByte));
   check(apex::fp8_quantize(x.data_ptr(), y.data_ptr<uint8_t>(), x.numel(), dt_code(x.scalar_type()), (int)fmt,
                            scale.data_ptr<float>(), o.scale_inv, o.amax, o.cur, (float)smax, cur_stream()),
@@ -1638,9 +1665,12 @@ Tensor k_fp8_quantize(Tensor x, int64_t fmt, Tensor scale, const c10::optional<T
 
 Tensor k_fp8_quantize_t(Tensor x, int64_t fmt, Tensor scale, const c10::optional<Tensor>& amax,
                         const c10::optional<Tensor>& cur_amax, const c10::optional<Tensor>& scale_inv, double smax) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2, "fp8_quantize_t: contiguous 2-D device tensor");
-  f8_check_scalar(scale, "scale");
-  const F8Opt o = f8_opts(amax, cur_amax, scale_inv, smax);
+  f8_check_input(x, "fp8_quantize_t");
+  TORCH_CHECK(x.dim() == 2 && x.size(0) < (1ll << 31) && x.size(1) < (1ll << 31),
+              "fp8_quantize_t: a 2-D tensor of fewer than 2^31 rows and columns");
+  f8_check_fmt(fmt, "fp8_quantize_t");
+  f8_check_scalar(scale, "scale", x);
+  const F8Opt o = f8_opts(x, amax, cur_amax, scale_inv, smax);
   Tensor y = at::empty({x.size(1), x.size(0)}, x.options().dtype(at::kByte));
   check(apex::fp8_quantize_t(x.data_ptr(), y.data_ptr<uint8_t>(), (int)x.size(0), (int)x.size(1),
                              dt_code(x.scalar_type()), (int)fmt, scale.data_ptr<float>(), o.scale_inv, o.amax, o.cur,
@@ -1657,10 +1687,11 @@ std::vector<Tensor> k_fp8_quantize_weights(const std::vector<Tensor>& ws, const 
                                            Tensor scale_inv, Tensor amax, double smax) {
   const size_t n = ws.size();
   TORCH_CHECK(slots.size() == n && want_t.size() == n, "fp8_quantize_weights: one slot / flag per weight");
-  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat && scale_inv.scalar_type() == at::kFloat &&
-                  amax.scalar_type() == at::kFloat && scale.is_contiguous() && scale_inv.is_contiguous() &&
-                  amax.is_contiguous(),
-              "fp8_quantize_weights: fp32 contiguous slot buffers");
+  f8_check_slots(scale, scale, 0, "fp8_quantize_weights", "scale");
+  f8_check_slots(scale_inv, scale, 0, "fp8_quantize_weights", "scale_inv");
+  f8_check_slots(amax, scale, 0, "fp8_quantize_weights", "amax");
+  f8_check_fmt(fmt, "fp8_quantize_weights");
+  TORCH_CHECK(smax > 0, "fp8_quantize_weights: smax > 0");
   std::vector<Tensor> out;
   out.reserve(2 * n);
   if (n == 0) return out;
@@ -1671,8 +1702,8 @@ std::vector<Tensor> k_fp8_quantize_weights(const std::vector<Tensor>& ws, const 
   for (size_t i = 0; i < n; ++i) {
     const Tensor& w = ws[i];
     TORCH_CHECK(w.is_cuda() && w.dim() == 2 && w.is_contiguous() && dt_code(w.scalar_type()) == dt &&
-                    w.device() == scale.device(),
-                "fp8_quantize_weights: contiguous 2-D device weights of one dtype");
+                    w.device() == scale.device() && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+                "fp8_quantize_weights: contiguous, 16-byte aligned 2-D weights of one dtype on the slot buffers' device");
     TORCH_CHECK(slots[i] >= 0 && slots[i] < scale.numel() && slots[i] < scale_inv.numel() && slots[i] < amax.numel(),
                 "fp8_quantize_weights: slot out of range");
     const int64_t R = w.size(0), C = w.size(1);
@@ -1695,8 +1726,8 @@ std::vector<Tensor> k_fp8_quantize_weights(const std::vector<Tensor>& ws, const 
 }
 
 void k_fp8_amax(Tensor x, Tensor amax) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous(), "fp8_amax: contiguous device tensor");
-  f8_check_scalar(amax, "amax");
+  f8_check_input(x, "fp8_amax");
+  f8_check_scalar(amax, "amax", x);
   check(apex::fp8_amax(x.data_ptr(), x.numel(), dt_code(x.scalar_type()), amax.data_ptr<float>(), cur_stream()),
         "fp8_amax");
 }
@@ -1705,7 +1736,13 @@ void k_fp8_update_scales(Tensor hist, Tensor amax_cur, Tensor scale, Tensor scal
                          int64_t idx, double margin_scale) {
   TORCH_CHECK(hist.is_cuda() && hist.dim() == 2 && hist.is_contiguous() && hist.scalar_type() == at::kFloat,
               "fp8_update_scales: hist fp32 [slots, history]");
-  TORCH_CHECK(n_slots <= hist.size(0) && idx >= 0 && idx < hist.size(1), "fp8_update_scales: bad slot count / index");
+  TORCH_CHECK(n_slots >= 0 && n_slots <= hist.size(0) && idx >= 0 && idx < hist.size(1) && hist.size(1) < (1ll << 31) &&
+                  n_slots < (1ll << 31),
+              "fp8_update_scales: bad slot count / index");
+  f8_check_slots(amax_cur, hist, n_slots, "fp8_update_scales", "amax_cur");
+  f8_check_slots(scale, hist, n_slots, "fp8_update_scales", "scale");
+  f8_check_slots(scale_inv, hist, n_slots, "fp8_update_scales", "scale_inv");
+  f8_check_slots(fmt_max, hist, n_slots, "fp8_update_scales", "fmt_max");
   check(apex::fp8_update_scales(hist.data_ptr<float>(), amax_cur.data_ptr<float>(), scale.data_ptr<float>(),
                                 scale_inv.data_ptr<float>(), fmt_max.data_ptr<float>(), (int)n_slots,
                                 (int)hist.size(1), (int)idx, (float)margin_scale, cur_stream()),
@@ -1764,7 +1801,8 @@ Tensor k_gemm_tt(Tensor a, Tensor b, int64_t splits, at::ScalarType out_dtype, c
 // b [R, Q] (fmt_b) — the codes the forward / backward GEMMs already consumed — split into `splits`
 // slices of fp32 partials, combined (and rounded to out_dtype) by splitk_reduce
 bool k_gemm_tt_f8_supported(Tensor a, Tensor b, int64_t splits) {
-  if (!a.is_cuda() || a.dim() != 2 || b.dim() != 2 || a.scalar_type() != at::kByte || b.scalar_type() != at::kByte)
+  if (!a.is_cuda() || b.device() != a.device() || a.dim() != 2 || b.dim() != 2 || a.scalar_type() != at::kByte ||
+      b.scalar_type() != at::kByte)
     return false;
   if (!a.is_contiguous() || !b.is_contiguous() || a.size(0) != b.size(0)) return false;
   auto al = [](const Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; };
@@ -1775,10 +1813,17 @@ bool k_gemm_tt_f8_supported(Tensor a, Tensor b, int64_t splits) {
 Tensor k_gemm_tt_f8(Tensor a, Tensor b, Tensor alpha_a, Tensor alpha_b, int64_t fmt_a, int64_t fmt_b, int64_t splits,
                     at::ScalarType out_dtype, const c10::optional<Tensor>& out_opt) {
   TORCH_CHECK(k_gemm_tt_f8_supported(a, b, splits), "gemm_tt_f8: unsupported operands");
-  TORCH_CHECK(alpha_a.is_cuda() && alpha_a.scalar_type() == at::kFloat && alpha_a.numel() >= 1 && alpha_b.is_cuda() &&
-                  alpha_b.scalar_type() == at::kFloat && alpha_b.numel() >= 1,
-              "gemm_tt_f8: alpha_a / alpha_b must be fp32 device scalars");
+  f8_check_scalar(alpha_a, "gemm_tt_f8: alpha_a", a);
+  f8_check_scalar(alpha_b, "gemm_tt_f8: alpha_b", a);
+  TORCH_CHECK((fmt_a == 0 || fmt_a == 1) && fmt_b == 0, "gemm_tt_f8: fmt_a 0 (e4m3) or 1 (e5m2), fmt_b 0");
   const int64_t R = a.size(0), P = a.size(1), Q = b.size(1);
+  // out_dtype and out (splitk_reduce stores 16-byte vectors) are checked before the GEMM is launched
+  dt_code(out_dtype);
+  if (out_opt.has_value() && out_opt->defined())
+    TORCH_CHECK(out_opt->device() == a.device() && out_opt->is_contiguous() && out_opt->scalar_type() == out_dtype &&
+                    out_opt->numel() == P * Q && reinterpret_cast<uintptr_t>(out_opt->data_ptr()) % 16 == 0,
+                "gemm_tt_f8: out must be a contiguous, 16-byte aligned tensor of P * Q elements of out_dtype on a's "
+                "device");
   apex::GemmArgs g{};
   g.A = a.data_ptr();
   g.B = b.data_ptr();

@@ -11,6 +11,14 @@
 //                 scale_inv = 1 / scale; amax_cur = 0
 // The conversions are the hardware v_cvt_pk_fp8_f32 / v_cvt_pk_bf8_f32 (round to nearest even); x
 // is clamped to the format's finite range first (e4m3fn has no infinity).
+// Non-finite elements (pinned by tests/test_fp8_numerics_gpu.py::test_nonfinite_elements):
+//   +-inf  saturates to +-max (0x7e / 0xfe e4m3, 0x7b / 0xfb e5m2) and makes the amax inf, which
+//          update records in the history as 0 (the overflowed step is skipped by the loss scaler;
+//          its amax must not poison the window); current scaling with an inf or NaN amax uses scale 1;
+//   NaN    is dropped by every amax (fmaxf / v_max3_f32 return the other operand) and its code is
+//          -max (0xfe / 0xfb): v_med3_f32 with a NaN operand returns the minimum of the other two.
+//          A NaN therefore never shows in the codes or in the amax: the overflow check of the 16-bit
+//          gradients (amp's loss scaler) is what skips such a step, not the fp8 path.
 #include "common.h"
 #include "kernels.h"
 #include "fp8_pack.h"

@@ -417,6 +417,12 @@ __device__ __forceinline__ void epilogue(const f32x4 (&acc)[NJ][8], char* reg, T
           }
           out = pack(v);
           if constexpr (COLSUM || Q8 != 0) {
+            // fp16: the packed words are made opaque first. Left to see through pack -> unpack, hipcc (ROCm 7)
+            // took elements 0 and 1 of the dGELU product from a v_fma_mixlo_f16 of their own (one rounding of
+            // the product to fp16) next to the v_cvt_pk_f16_f32 of the fp32 product that is stored (two
+            // roundings): the bias gradient then summed values that differ from the stored dh by an fp16 ulp
+            // where the two disagree (persistent fp8 kernel with Q8 codes, edge-tile kernels)
+            if constexpr (__is_same(T, f16)) asm("" : "+v"(out));
             float r[8];
             unpack(out, r);  // the bias grad / the fp8 codes take the stored (rounded) values
             if constexpr (COLSUM) {
@@ -431,9 +437,12 @@ __device__ __forceinline__ void epilogue(const f32x4 (&acc)[NJ][8], char* reg, T
             }
             if constexpr (Q8 != 0 && !COLSUM) {
               typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+              // edge tiles: a chunk past N holds column N - 1's sums under the last chunk's bias (clamped
+              // staging, bias read at N - 8) — values of no element of C, kept out of max|C|
+              const bool in_c = F || (wrow0 + lrow + 8 * slot < M && ncol < N);
 #pragma unroll
               for (int e = 0; e < 8; ++e) {
-                q8mx = fmaxf(q8mx, fabsf(r[e]));
+                q8mx = fmaxf(q8mx, in_c ? fabsf(r[e]) : 0.f);
                 r[e] *= q8s;
               }
               const u32x2 w = u32x2{f8_pack4<Q8 - 1>(r[0], r[1], r[2], r[3]), f8_pack4<Q8 - 1>(r[4], r[5], r[6], r[7])};

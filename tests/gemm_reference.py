@@ -211,13 +211,15 @@ def acc_ref(A, B):
     return a @ b.t(), a.abs() @ b.abs().t()
 
 
-def expected(epi, T, K, acc, cond, bias=None, aux=None, got=None):
+def expected(epi, T, K, acc, cond, bias=None, aux=None, got=None, stage=0.0):
     """The outputs of one epilogue as {name: (ref, bound)}: "C", and "X" (H of BIAS_GELU, G of BIAS_GELU_D).
     bias [N] and aux [M, N] at their stored values; ``got`` = {"X": the H the kernel stored} is needed by
-    BIAS_GELU, whose Y is held to the GELU of that H."""
+    BIAS_GELU, whose Y is held to the GELU of that H. ``stage``: the relative error of an fp32 operation on the
+    accumulator before its rounding to T (0 for the 16-bit kernels; the fp8 kernels' alpha multiply, 2**-24:
+    tests/fp8_reference.py)."""
     u, tiny = HALF_ULP[T], TINY[T]
     delta = K * E23 * cond
-    r1 = u * acc.abs() + delta
+    r1 = (u + stage) * acc.abs() + delta
     tanh = is_tanh(epi)
     if epi == "none":
         return {"C": (acc, r1 + tiny)}
@@ -252,10 +254,11 @@ def bias_grad_expected(dh_stored, bdt):
     return ref, dh.shape[0] * E24 * dh.abs().sum(0) + HALF_ULP[bdt] * ref.abs() + TINY[bdt]
 
 
-def check_epilogue(epi, T, K, acc, cond, got_c, got_x, bias=None, aux=None, bdt=None, what="", tag=None, worst=None):
+def check_epilogue(epi, T, K, acc, cond, got_c, got_x, bias=None, aux=None, bdt=None, what="", tag=None, worst=None,
+                   stage=0.0):
     """Hold every output of one GEMM call to its bound. got_c: C; got_x: H / G / the bias gradient (dtype bdt).
     ``worst`` (a dict) collects ratios instead of asserting (the mutant tests). Returns the largest ratio."""
-    exp = expected(epi, T, K, acc, cond, bias, aux, {"X": got_x} if gelu_fwd(epi) and not gelu_d(epi) else None)
+    exp = expected(epi, T, K, acc, cond, bias, aux, {"X": got_x} if gelu_fwd(epi) and not gelu_d(epi) else None, stage)
     outs = [("C", got_c.reshape(acc.shape), *exp["C"])]
     if "X" in exp:
         outs.append(("X", got_x.reshape(acc.shape), *exp["X"]))
