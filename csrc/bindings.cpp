@@ -1725,6 +1725,69 @@ std::vector<Tensor> k_fp8_quantize_weights(const std::vector<Tensor>& ws, const 
   return out;
 }
 
+// ---- MXFP8 (mx.hip, gemm_mx.hip) ----
+bool k_mx_quantize_supported(int64_t R, int64_t C, bool rowwise, bool colwise) {
+  return apex::mx_quantize_supported(R, C, rowwise, colwise);
+}
+
+// x [R, C] -> [codes, scales] per requested orientation (rowwise first), from one launch
+std::vector<Tensor> k_mx_quantize(Tensor x, int64_t fmt, bool rowwise, bool colwise) {
+  f8_check_input(x, "mx_quantize");
+  f8_check_fmt(fmt, "mx_quantize");
+  TORCH_CHECK(x.dim() == 2 && apex::mx_quantize_supported(x.size(0), x.size(1), rowwise, colwise),
+              "mx_quantize: a non-empty 2-D tensor; rowwise needs C % 32 == 0, colwise R % 32 == 0");
+  const int64_t R = x.size(0), C = x.size(1);
+  auto opt = x.options().dtype(at::kByte);
+  std::vector<Tensor> out;
+  uint8_t *yr = nullptr, *sr = nullptr, *yc = nullptr, *sc = nullptr;
+  if (rowwise) {
+    out.push_back(at::empty({R, C}, opt));
+    out.push_back(at::empty({R, C / 32}, opt));
+    yr = out[0].data_ptr<uint8_t>();
+    sr = out[1].data_ptr<uint8_t>();
+  }
+  if (colwise) {
+    out.push_back(at::empty({C, R}, opt));
+    out.push_back(at::empty({C, R / 32}, opt));
+    yc = out[out.size() - 2].data_ptr<uint8_t>();
+    sc = out[out.size() - 1].data_ptr<uint8_t>();
+  }
+  check(apex::mx_quantize(x.data_ptr(), (int)R, (int)C, dt_code(x.scalar_type()), (int)fmt, yr, sr, yc, sc, cur_stream()),
+        "mx_quantize");
+  return out;
+}
+
+bool k_gemm_mx_supported(Tensor a, Tensor sa, Tensor b, Tensor sb) {
+  auto ok = [&](const Tensor& t) {
+    return t.is_cuda() && t.device() == a.device() && t.dim() == 2 && t.scalar_type() == at::kByte && t.is_contiguous() &&
+           reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+  };
+  if (!(ok(a) && ok(sa) && ok(b) && ok(sb))) return false;
+  const int64_t M = a.size(0), K = a.size(1), N = b.size(0);
+  if (b.size(1) != K || sa.size(0) != M || sb.size(0) != N || sa.size(1) * 32 != K || sb.size(1) * 32 != K) return false;
+  return apex::gemm_mx_supported(M, N, K);
+}
+
+Tensor k_gemm_mx(Tensor a, Tensor sa, Tensor b, Tensor sb, int64_t fmt_a, int64_t fmt_b, const c10::optional<Tensor>& bias,
+                 at::ScalarType out_dtype) {
+  TORCH_CHECK(k_gemm_mx_supported(a, sa, b, sb),
+              "gemm_mx: unsupported operands (contiguous, 16-byte aligned uint8 codes [M, K] / [N, K] and scales "
+              "[M, K / 32] / [N, K / 32] on one device, K % 128 == 0, N % 8 == 0)");
+  f8_check_fmt(fmt_a, "gemm_mx");
+  f8_check_fmt(fmt_b, "gemm_mx");
+  const int64_t M = a.size(0), K = a.size(1), N = b.size(0);
+  Tensor c = at::empty({M, N}, a.options().dtype(out_dtype));
+  apex::MxGemmArgs g{a.data_ptr<uint8_t>(), b.data_ptr<uint8_t>(), sa.data_ptr<uint8_t>(), sb.data_ptr<uint8_t>(),
+                     c.data_ptr(), nullptr, (int)M, (int)N, (int)K, (int)fmt_a, (int)fmt_b};
+  if (bias.has_value() && bias->defined()) {
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N && bias->scalar_type() == out_dtype && gemm_operand_ok(a, *bias),
+                "gemm_mx: bias must be a contiguous, 16-byte aligned [N] tensor of out_dtype on a's device");
+    g.bias = bias->data_ptr();
+  }
+  check(apex::gemm_mx(g, dt_code(out_dtype), cur_stream()), "gemm_mx");
+  return c;
+}
+
 void k_fp8_amax(Tensor x, Tensor amax) {
   f8_check_input(x, "fp8_amax");
   f8_check_scalar(amax, "amax", x);
@@ -1929,6 +1992,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fp8_quantize_t", &k_fp8_quantize_t, py::arg("x"), py::arg("fmt"), py::arg("scale"),
         py::arg("amax") = py::none(), py::arg("cur_amax") = py::none(), py::arg("scale_inv") = py::none(),
         py::arg("smax") = 0.0);
+  m.def("mx_quantize_supported", &k_mx_quantize_supported, py::arg("R"), py::arg("C"), py::arg("rowwise"), py::arg("colwise"));
+  m.def("mx_quantize", &k_mx_quantize, py::arg("x"), py::arg("fmt"), py::arg("rowwise") = true, py::arg("colwise") = false);
+  m.def("gemm_mx_supported", &k_gemm_mx_supported);
+  m.def("gemm_mx", &k_gemm_mx, py::arg("a"), py::arg("a_scales"), py::arg("b"), py::arg("b_scales"), py::arg("fmt_a"),
+        py::arg("fmt_b"), py::arg("bias") = py::none(), py::arg("out_dtype") = at::kBFloat16);
   m.def("fp8_amax", &k_fp8_amax);
   m.def("fp8_update_scales", &k_fp8_update_scales);
   m.def("flash_attn_fwd", &flash_attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),

@@ -348,6 +348,26 @@ bool gemm_tt_supported(int P, int Q, int R, int splits, int64_t lda, int64_t ldb
 int gemm_tt(const GemmArgs& g, int dt, hipStream_t s);
 bool gemm_tt_f8_supported(int P, int Q, int R, int splits, int64_t lda, int64_t ldb);
 int gemm_tt_f8(const GemmArgs& g, int fmt_a, int fmt_b, hipStream_t s);
+// MXFP8 (OCP Microscaling: 1 x 32 blocks, one E8M0 scale byte each; fmt 0 = e4m3, 1 = e5m2)
+// mx.hip: x [R, C] -> rowwise codes yr [R, C] + scales sr [R, C / 32] (C % 32 == 0) and / or colwise codes
+// yc [C, R] + scales sc [C, R / 32] (R % 32 == 0) in one launch; a null yr / yc skips that orientation
+bool mx_quantize_supported(int64_t R, int64_t C, bool rowwise, bool colwise);
+int mx_quantize(const void* x, int R, int C, int dt, int fmt, uint8_t* yr, uint8_t* sr, uint8_t* yc, uint8_t* sc,
+                hipStream_t s);
+// gemm_mx.hip: C [M, N] = (A8 . 2^(SA - 127)) (B8 . 2^(SB - 127))^T (+ bias), A8 [M, K], B8 [N, K],
+// SA [M, K / 32], SB [N, K / 32], all contiguous; K % 128 == 0, N % 8 == 0; bias [N] in the output dtype
+struct MxGemmArgs {
+  const uint8_t* A;
+  const uint8_t* B;
+  const uint8_t* SA;
+  const uint8_t* SB;
+  void* C;
+  const void* bias;
+  int M, N, K;
+  int fmt_a, fmt_b;
+};
+bool gemm_mx_supported(int64_t M, int64_t N, int64_t K);
+int gemm_mx(const MxGemmArgs& g, int out_dt, hipStream_t s);
 int gemm_bias_grad(const float* part, int parts, int N, void* out, int odt, hipStream_t s);
 int transpose_2d(const void* in, void* out, int R, int C, int dt, hipStream_t s);
 

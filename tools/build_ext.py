@@ -25,6 +25,9 @@ CSRC = os.path.join(ROOT, "csrc")
 BUILD = os.path.join(ROOT, "build", "obj")
 ARCH = os.environ.get("APEX_OFFLOAD_ARCH", "gfx950")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
+# units compiled with the packed fp32 VALU forms (v_pk_mul_f32 and kin) turned off: the MX quantiser's
+# codes are a bit-exact contract, and the scaling multiplies are where the compiler would pack
+NO_PACKED_F32 = {"mx.hip", "gemm_mx.hip"}
 
 
 def _torch_paths():
@@ -71,6 +74,8 @@ def build(jobs: int | None = None, force: bool = False, verbose: bool = False) -
         objs.append(obj)
         if force or _newer(obj, [src] + headers):
             cmd = [hipcc, f"--offload-arch={ARCH}", "-c", src, "-o", obj, "-munsafe-fp-atomics"] + common
+            if os.path.basename(src) in NO_PACKED_F32:
+                cmd += ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
             steps.append(cmd)
     bind = os.path.join(CSRC, "bindings.cpp")
     bobj = os.path.join(BUILD, "bindings.cpp.o")
