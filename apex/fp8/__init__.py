@@ -662,7 +662,7 @@ def fp8_autocast(enabled: bool = True, recipe: Fp8Recipe | None = None, device=N
         _DEPTH -= 1
 
 
-# MXFP8 (block-scaled operands, apex/fp8/mx.py): re-exports only
-from .mx import MXLinear, mx_dequantize, mx_gemm, mx_linear, mx_quantize, mx_supported  # noqa: E402
+# MXFP8 / MXFP4 (block-scaled operands, apex/fp8/mx.py): re-exports only
+from .mx import E2M1, MXLinear, mx_dequantize, mx_gemm, mx_linear, mx_quantize, mx_supported  # noqa: E402
 
-__all__ += ["mx_quantize", "mx_dequantize", "mx_gemm", "mx_supported", "mx_linear", "MXLinear"]
+__all__ += ["mx_quantize", "mx_dequantize", "mx_gemm", "mx_supported", "mx_linear", "MXLinear", "E2M1"]

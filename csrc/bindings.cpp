@@ -1733,21 +1733,21 @@ bool k_mx_quantize_supported(int64_t R, int64_t C, bool rowwise, bool colwise) {
 // x [R, C] -> [codes, scales] per requested orientation (rowwise first), from one launch
 std::vector<Tensor> k_mx_quantize(Tensor x, int64_t fmt, bool rowwise, bool colwise) {
   f8_check_input(x, "mx_quantize");
-  f8_check_fmt(fmt, "mx_quantize");
+  TORCH_CHECK(fmt >= 0 && fmt <= 2, "mx_quantize: fmt 0 (e4m3), 1 (e5m2) or 2 (e2m1)");
   TORCH_CHECK(x.dim() == 2 && apex::mx_quantize_supported(x.size(0), x.size(1), rowwise, colwise),
               "mx_quantize: a non-empty 2-D tensor; rowwise needs C % 32 == 0, colwise R % 32 == 0");
-  const int64_t R = x.size(0), C = x.size(1);
+  const int64_t R = x.size(0), C = x.size(1), pk = fmt == 2 ? 2 : 1;  // e2m1: two codes per byte
   auto opt = x.options().dtype(at::kByte);
   std::vector<Tensor> out;
   uint8_t *yr = nullptr, *sr = nullptr, *yc = nullptr, *sc = nullptr;
   if (rowwise) {
-    out.push_back(at::empty({R, C}, opt));
+    out.push_back(at::empty({R, C / pk}, opt));
     out.push_back(at::empty({R, C / 32}, opt));
     yr = out[0].data_ptr<uint8_t>();
     sr = out[1].data_ptr<uint8_t>();
   }
   if (colwise) {
-    out.push_back(at::empty({C, R}, opt));
+    out.push_back(at::empty({C, R / pk}, opt));
     out.push_back(at::empty({C, R / 32}, opt));
     yc = out[out.size() - 2].data_ptr<uint8_t>();
     sc = out[out.size() - 1].data_ptr<uint8_t>();
@@ -1785,6 +1785,39 @@ Tensor k_gemm_mx(Tensor a, Tensor sa, Tensor b, Tensor sb, int64_t fmt_a, int64_
     g.bias = bias->data_ptr();
   }
   check(apex::gemm_mx(g, dt_code(out_dtype), cur_stream()), "gemm_mx");
+  return c;
+}
+
+// ---- MXFP4 (gemm_mx4.hip): b packed e2m1 [N, K / 2]; a packed e2m1 [M, K / 2] (fmt_a 2) or fp8 [M, K] ----
+bool k_gemm_mx4_supported(Tensor a, Tensor sa, Tensor b, Tensor sb, int64_t fmt_a) {
+  auto ok = [&](const Tensor& t) {
+    return t.is_cuda() && t.device() == a.device() && t.dim() == 2 && t.scalar_type() == at::kByte && t.is_contiguous() &&
+           reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+  };
+  if (fmt_a < 0 || fmt_a > 2 || !(ok(a) && ok(sa) && ok(b) && ok(sb))) return false;
+  const int64_t M = a.size(0), K = b.size(1) * 2, N = b.size(0);
+  if (a.size(1) * (fmt_a == 2 ? 2 : 1) != K || sa.size(0) != M || sb.size(0) != N || sa.size(1) * 32 != K ||
+      sb.size(1) * 32 != K)
+    return false;
+  return apex::gemm_mx4_supported(M, N, K, (int)fmt_a);
+}
+
+Tensor k_gemm_mx4(Tensor a, Tensor sa, Tensor b, Tensor sb, int64_t fmt_a, const c10::optional<Tensor>& bias,
+                  at::ScalarType out_dtype) {
+  TORCH_CHECK(k_gemm_mx4_supported(a, sa, b, sb, fmt_a),
+              "gemm_mx4: unsupported operands (contiguous, 16-byte aligned uint8 codes a [M, K / 2] e2m1 or [M, K] fp8, "
+              "b [N, K / 2] e2m1 and scales [M, K / 32] / [N, K / 32] on one device, K % 256 == 0 for e2m1 x e2m1, "
+              "K % 128 == 0 for fp8 x e2m1, N % 8 == 0)");
+  const int64_t M = a.size(0), K = b.size(1) * 2, N = b.size(0);
+  Tensor c = at::empty({M, N}, a.options().dtype(out_dtype));
+  apex::MxGemmArgs g{a.data_ptr<uint8_t>(), b.data_ptr<uint8_t>(), sa.data_ptr<uint8_t>(), sb.data_ptr<uint8_t>(),
+                     c.data_ptr(), nullptr, (int)M, (int)N, (int)K, (int)fmt_a, 2};
+  if (bias.has_value() && bias->defined()) {
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N && bias->scalar_type() == out_dtype && gemm_operand_ok(a, *bias),
+                "gemm_mx4: bias must be a contiguous, 16-byte aligned [N] tensor of out_dtype on a's device");
+    g.bias = bias->data_ptr();
+  }
+  check(apex::gemm_mx4(g, dt_code(out_dtype), cur_stream()), "gemm_mx4");
   return c;
 }
 
@@ -1997,6 +2030,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_mx_supported", &k_gemm_mx_supported);
   m.def("gemm_mx", &k_gemm_mx, py::arg("a"), py::arg("a_scales"), py::arg("b"), py::arg("b_scales"), py::arg("fmt_a"),
         py::arg("fmt_b"), py::arg("bias") = py::none(), py::arg("out_dtype") = at::kBFloat16);
+  m.def("gemm_mx4_supported", &k_gemm_mx4_supported);
+  m.def("gemm_mx4", &k_gemm_mx4, py::arg("a"), py::arg("a_scales"), py::arg("b"), py::arg("b_scales"), py::arg("fmt_a"),
+        py::arg("bias") = py::none(), py::arg("out_dtype") = at::kBFloat16);
   m.def("fp8_amax", &k_fp8_amax);
   m.def("fp8_update_scales", &k_fp8_update_scales);
   m.def("flash_attn_fwd", &flash_attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),

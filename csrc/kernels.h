@@ -348,7 +348,8 @@ bool gemm_tt_supported(int P, int Q, int R, int splits, int64_t lda, int64_t ldb
 int gemm_tt(const GemmArgs& g, int dt, hipStream_t s);
 bool gemm_tt_f8_supported(int P, int Q, int R, int splits, int64_t lda, int64_t ldb);
 int gemm_tt_f8(const GemmArgs& g, int fmt_a, int fmt_b, hipStream_t s);
-// MXFP8 (OCP Microscaling: 1 x 32 blocks, one E8M0 scale byte each; fmt 0 = e4m3, 1 = e5m2)
+// MXFP8 / MXFP4 (OCP Microscaling: 1 x 32 blocks, one E8M0 scale byte each; fmt 0 = e4m3, 1 = e5m2, 2 = e2m1
+// packed two codes to a byte: the code arrays are then [R, C / 2] and [C, R / 2])
 // mx.hip: x [R, C] -> rowwise codes yr [R, C] + scales sr [R, C / 32] (C % 32 == 0) and / or colwise codes
 // yc [C, R] + scales sc [C, R / 32] (R % 32 == 0) in one launch; a null yr / yc skips that orientation
 bool mx_quantize_supported(int64_t R, int64_t C, bool rowwise, bool colwise);
@@ -368,6 +369,11 @@ struct MxGemmArgs {
 };
 bool gemm_mx_supported(int64_t M, int64_t N, int64_t K);
 int gemm_mx(const MxGemmArgs& g, int out_dt, hipStream_t s);
+// gemm_mx4.hip: the same product with B packed e2m1 codes [N, K / 2] (fmt_b = 2; two codes per byte, the even
+// element in the low nibble) and A either e2m1 [M, K / 2] (fmt_a = 2, K % 256 == 0) or fp8 [M, K] (fmt_a =
+// 0 / 1, K % 128 == 0); g.K is the contraction length in elements
+bool gemm_mx4_supported(int64_t M, int64_t N, int64_t K, int fmt_a);
+int gemm_mx4(const MxGemmArgs& g, int out_dt, hipStream_t s);
 int gemm_bias_grad(const float* part, int parts, int N, void* out, int odt, hipStream_t s);
 int transpose_2d(const void* in, void* out, int R, int C, int dt, hipStream_t s);
 
