@@ -27,6 +27,7 @@ from ..ops import fused as fops
 from ..transformer import parallel_state as ps
 from ..transformer import tensor_parallel as tp
 from ..transformer.functional import fused_rope
+from ..transformer.moe import MoEMLP
 
 
 # APEX_MEGATRON_FUSED_LN=0: per-layer forward (separate LayerNorms; A/B and fallback switch)
@@ -54,6 +55,10 @@ class MegatronGPTConfig:
     rotary_base: int = 10000
     num_query_groups: int | None = None  # grouped-query attention: key/value heads (None = num_attention_heads)
     activation: str = "gelu"  # "gelu" | "swiglu" | "geglu" (gated: dense_h_to_4h emits [gate | up], erf GELU)
+    # mixture of experts: every layer's MLP becomes apex.transformer.moe.MoEMLP (layer.mlp.router / w1 / w2
+    # instead of dense_h_to_4h / dense_4h_to_h) with this many experts; tensor-parallel size 1 only
+    num_moe_experts: int | None = None
+    moe_router_topk: int = 2
 
     def __post_init__(self):
         if self.activation not in _ACTIVATIONS:
@@ -111,7 +116,16 @@ class ParallelTransformerLayer(nn.Module):
         self.dense = tp.RowParallelLinear(c.hidden_size, c.hidden_size, input_is_parallel=True,
                                           init_method=_init(out_std), skip_bias_add=True, params_dtype=c.params_dtype)
         self.post_attention_layernorm = FusedLayerNorm(c.hidden_size, eps=c.layernorm_epsilon)
+        self.p_hidden, self.p_attn = c.hidden_dropout, c.attention_dropout
         self.gated_act = _ACTIVATIONS[c.activation]
+        self.mlp = None
+        if c.num_moe_experts is not None:
+            if tpws > 1:
+                raise ValueError("num_moe_experts needs a tensor-parallel world size of 1 (experts are not sharded), "
+                                 f"got {tpws}")
+            self.mlp = MoEMLP(c.hidden_size, c.ffn_hidden_size, c.num_moe_experts, c.moe_router_topk, c.activation,
+                              init_std=c.init_method_std, out_std=out_std, params_dtype=c.params_dtype)
+            return
         if self.gated_act is not None and c.ffn_hidden_size % tpws:
             raise ValueError(f"ffn_hidden_size={c.ffn_hidden_size} must be a multiple of the tensor-parallel "
                              f"world size {tpws}")
@@ -122,7 +136,6 @@ class ParallelTransformerLayer(nn.Module):
         self.dense_4h_to_h = tp.RowParallelLinear(c.ffn_hidden_size, c.hidden_size, input_is_parallel=True,
                                                   init_method=_init(out_std), skip_bias_add=True,
                                                   params_dtype=c.params_dtype)
-        self.p_hidden, self.p_attn = c.hidden_dropout, c.attention_dropout
 
     def _rotate(self, qkv, rope):
         # rope = (cos, sin) [S, d2] fp32 or None (learned positions). RoPE is per head, so the
@@ -160,10 +173,10 @@ class ParallelTransformerLayer(nn.Module):
         out, bias = self.dense(ctx.reshape(B, S, -1))
         x = fops.bias_dropout_add(out, bias, x, ph)
         xn = self.post_attention_layernorm(x)
-        f1, f2 = self.dense_h_to_4h, self.dense_4h_to_h
-        if self.gated_act is not None:
-            out, bias = self._gated_mlp(xn)
+        if self.mlp is not None or self.gated_act is not None:
+            out, bias = self.mlp(xn) if self.mlp is not None else self._gated_mlp(xn)
             return fops.bias_dropout_add(out, bias, x, ph)
+        f1, f2 = self.dense_h_to_4h, self.dense_4h_to_h
         if not (f1.sequence_parallel_enabled or f2.sequence_parallel_enabled) and f1.bias is not None:
             # whole MLP shard as one Function (GEMM+bias+GELU epilogue, dGELU epilogue in backward)
             # between the same TP mappings the two parallel linears apply
@@ -188,9 +201,11 @@ class ParallelTransformerLayer(nn.Module):
         out, bias = self.dense(ctx.reshape(B, S, -1))
         ln2 = self.post_attention_layernorm
         x, xn = fops.bias_dropout_add_ln(out, bias, x, ln2.weight, ln2.bias, ph, ln2.eps)
-        f1, f2 = self.dense_h_to_4h, self.dense_4h_to_h
+        f1, f2 = getattr(self, "dense_h_to_4h", None), getattr(self, "dense_4h_to_h", None)  # (None with experts)
         t = bias2 = None
-        if self.gated_act is not None:
+        if self.mlp is not None:
+            t, bias2 = self.mlp(xn)
+        elif self.gated_act is not None:
             t, bias2 = self._gated_mlp(xn)
         elif not (f1.sequence_parallel_enabled or f2.sequence_parallel_enabled) and f1.bias is not None:
             t = fblocks.mlp(tp.copy_to_tensor_model_parallel_region(xn), f1.weight, f1.bias, f2.weight)

@@ -1,0 +1,234 @@
+"""Grouped linear layers over expert-sorted rows, and the token permutation around them (mixture of experts).
+
+The segment layout every function here shares: expert-sorted activations are a 2-D tensor ``x [R, K]`` plus
+``offsets``, an int32 device tensor ``[E + 1]`` with ``offsets[0] == 0``, non-decreasing entries that are all
+multiples of 64, and ``offsets[E] <= R``. Expert ``e`` owns rows ``[offsets[e], offsets[e + 1])`` (possibly
+none); the rows that pad a segment up to its multiple of 64 hold zeros; rows from ``offsets[E]`` on are an
+unused tail that every op here writes as zeros. ``R`` is a static upper bound, so no shape depends on the
+routing, and ``offsets`` is never read on the host: there is no sync, and everything here can be captured in
+a ``torch.cuda.graph``.
+
+  grouped_linear(x, weight, offsets)         y[seg_e] = x[seg_e] @ weight[e].T,  weight [E, N, K], no bias
+  moe_permute(x, expert_ids, num_experts)    tokens [T, H] -> (xp [R, H], offsets, dest [T, topk])
+  moe_unpermute(yp, dest, probs)             out[t] = sum_k probs[t, k] * yp[dest[t, k]]
+
+Device tensors in bf16 / fp16 run on the HIP kernels of csrc/gemm_grouped.hip (one launch per GEMM: forward,
+input gradient, weight gradient) and csrc/moe.hip. CPU tensors, ``APEX_FORCE_REFERENCE=1`` and the shapes
+``grouped_gemm_supported`` declines take the PyTorch formulation below, which keeps the same contract (zero
+pads, zero tail, no host read of ``offsets``).
+"""
+from __future__ import annotations
+
+import torch
+
+from .. import _ext
+from .fused import main_grad_placeholder
+
+_HALF = (torch.bfloat16, torch.float16)
+
+
+def grouped_gemm_supported(R, K, N, E):
+    """Can the grouped MFMA kernels run ``[R, K] x [E, N, K]``? ``K % 64 == 0``, ``N % 8 == 0``, ``E >= 1``,
+    ``R % 64 == 0`` and the kernels' size limits. Needs the built extension."""
+    return bool(_ext.require().gemm_grouped_supported(int(R), int(K), int(N), int(E)))
+
+
+def _native_gemm(a, R, K, N, E):
+    return (_ext.use_native(a) and a.dtype in _HALF and a.is_contiguous() and a.data_ptr() % 16 == 0
+            and grouped_gemm_supported(R, K, N, E))
+
+
+def _row_expert(offsets, R):
+    """Expert of every row ([R] int64; E for the tail), from the device-side table."""
+    rows = torch.arange(R, device=offsets.device, dtype=offsets.dtype)
+    return torch.bucketize(rows, offsets[1:].contiguous(), right=True)
+
+
+def _nt_reference(x, w, offsets):
+    """y[seg_e] = x[seg_e] @ w[e].T with a 0/1 row mask per expert (no host read of offsets); fp32 math for
+    16-bit operands, rounded once; tail rows come out zero."""
+    ct = torch.float32 if x.dtype in _HALF else x.dtype
+    eid = _row_expert(offsets, x.shape[0])
+    xf = x.to(ct)
+    y = torch.zeros(x.shape[0], w.shape[1], dtype=ct, device=x.device)
+    for e in range(w.shape[0]):
+        y = y + (xf * (eid == e).to(ct)[:, None]) @ w[e].to(ct).t()
+    return y.to(x.dtype)
+
+
+def _tt_reference(dy, x, offsets, E):
+    """dw[e] = dy[seg_e].T @ x[seg_e] in fp32 (float64 operands: float64), [E, N, K]."""
+    ct = torch.float64 if x.dtype == torch.float64 else torch.float32
+    eid = _row_expert(offsets, x.shape[0])
+    xf, dyf = x.to(ct), dy.to(ct)
+    return torch.stack([(dyf * (eid == e).to(ct)[:, None]).t() @ xf for e in range(E)])
+
+
+def _grouped_nt(x, w, offsets):
+    if _native_gemm(x, x.shape[0], x.shape[1], w.shape[1], w.shape[0]) and w.is_contiguous() and w.data_ptr() % 16 == 0:
+        return _ext.require().gemm_grouped_nt(x, w, offsets)
+    return _nt_reference(x, w, offsets)
+
+
+class _GroupedLinear(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, offsets):
+        xc = x.contiguous()
+        ctx.save_for_backward(xc, weight, offsets)
+        ctx.param = weight
+        return _grouped_nt(xc, weight.contiguous(), offsets)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, offsets = ctx.saved_tensors
+        E, N, K = w.shape
+        dy = dy.contiguous()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            # the dense layers' convention: a per-step transposed copy of the weight, then the NT kernel
+            dx = _grouped_nt(dy, w.transpose(1, 2).contiguous(), offsets)
+        if ctx.needs_input_grad[1]:
+            native = _native_gemm(x, x.shape[0], K, N, E) and dy.data_ptr() % 16 == 0
+            mg = getattr(ctx.param, "main_grad", None)
+            if mg is not None:
+                if native and mg.dtype == torch.float32 and mg.is_contiguous() and mg.data_ptr() % 16 == 0 \
+                        and mg.numel() == w.numel():
+                    _ext.require().gemm_grouped_tt(dy, x, offsets, acc=mg)
+                else:
+                    mg.add_(_tt_reference(dy, x, offsets, E).view_as(mg).to(mg.dtype))
+                dw = main_grad_placeholder(ctx.param)
+            elif native:
+                dw = _ext.require().gemm_grouped_tt(dy, x, offsets)
+            else:
+                dw = _tt_reference(dy, x, offsets, E).to(w.dtype)
+        return dx, dw, None
+
+
+def grouped_linear(x, weight, offsets):
+    """``y[offsets[e]:offsets[e+1]] = x[offsets[e]:offsets[e+1]] @ weight[e].T`` for ``x [R, K]``, ``weight
+    [E, N, K]`` and the int32 device table ``offsets [E + 1]`` of the module docstring; returns ``[R, N]`` with
+    zero tail rows. No bias. Differentiable in ``x`` and ``weight``: the input gradient runs the same grouped
+    kernel against a transposed copy of the weight, the weight gradient the grouped transposed-read kernel,
+    accumulated in fp32 into ``weight.main_grad`` (a placeholder gradient is returned) when the parameter
+    carries one. An expert without rows gets a zero gradient and leaves its ``main_grad`` slab untouched."""
+    if x.dim() != 2 or weight.dim() != 3 or weight.shape[2] != x.shape[1]:
+        raise ValueError(f"grouped_linear: x [R, K] and weight [E, N, K], got {tuple(x.shape)} and {tuple(weight.shape)}")
+    if offsets.dtype != torch.int32 or offsets.shape != (weight.shape[0] + 1,) or offsets.device != x.device:
+        raise ValueError("grouped_linear: offsets must be an int32 [E + 1] tensor on x's device")
+    return _GroupedLinear.apply(x, weight, offsets)
+
+
+# ---------------------------------------------------------------------------
+# token permutation
+def _native_rows(src, rows):
+    return _ext.use_native(src) and src.is_contiguous() and src.data_ptr() % 16 == 0 and \
+        _ext.require().moe_rows_supported(src, rows)
+
+
+def _gather(src, row_of, scale=None):
+    """out[r] = scale[r] * src[row_of[r]], zeros where row_of[r] < 0."""
+    src = src.contiguous()
+    if _native_rows(src, row_of.numel()):
+        return _ext.require().moe_gather(src, row_of, scale)
+    out = src[row_of.clamp(min=0).long()]
+    if scale is not None:
+        out = (out.float() * scale[:, None]).to(src.dtype)
+    return torch.where((row_of >= 0)[:, None], out, torch.zeros_like(out))
+
+
+def _combine(src, dest, w=None, g=None, want_out=True):
+    """(sum_k w[t, k] * src[dest[t, k]] or None, <g[t], src[dest[t, k]]> in fp32 or None)."""
+    src = src.contiguous()
+    if g is not None:
+        g = g.contiguous()
+    if _native_rows(src, dest.shape[0]) and dest.shape[1] <= 8 and (g is None or g.data_ptr() % 16 == 0):
+        return tuple(_ext.require().moe_combine(src, dest, w, g, want_out))
+    ct = torch.float32 if src.dtype in _HALF else src.dtype
+    rows = src[dest.long()].to(ct)                       # [T, topk, H]
+    out = dw = None
+    if want_out:
+        out = (rows if w is None else rows * w.to(ct)[..., None]).sum(1).to(src.dtype)
+    if g is not None:
+        dw = (rows * g.to(ct)[:, None, :]).sum(-1).float()
+    return out, dw
+
+
+def _routing_maps(expert_ids, num_experts):
+    """(offsets int32 [E + 1], dest int32 [T, topk], token_of_row int32 [R], R) for expert ids [T, topk]: a
+    stable sort of the flat ids, per-expert counts rounded up to 64, their running sum. All on the device."""
+    T, topk = expert_ids.shape
+    E, n = num_experts, T * topk
+    R = (n + 63) // 64 * 64 + 64 * E
+    flat = expert_ids.reshape(-1).long()
+    dev = flat.device
+    order = torch.argsort(flat, stable=True)
+    counts = torch.zeros(E, dtype=torch.long, device=dev).scatter_add_(0, flat, torch.ones_like(flat))
+    ends = torch.cumsum((counts + 63) // 64 * 64, 0)
+    offsets = torch.cat([ends.new_zeros(1), ends])
+    sorted_e = flat[order]
+    first = torch.cumsum(counts, 0) - counts               # position of each expert's first row in the sort
+    row = offsets[sorted_e] + torch.arange(n, device=dev) - first[sorted_e]
+    dest = torch.empty(n, dtype=torch.int32, device=dev)
+    dest[order] = row.int()
+    token_of_row = torch.full((R,), -1, dtype=torch.int32, device=dev)
+    token_of_row[row] = (order // topk).int()
+    return offsets.int(), dest.view(T, topk), token_of_row, R
+
+
+class _Permute(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, dest, token_of_row):
+        ctx.save_for_backward(dest)
+        return _gather(x, token_of_row)
+
+    @staticmethod
+    def backward(ctx, dxp):
+        (dest,) = ctx.saved_tensors
+        return _combine(dxp, dest)[0], None, None
+
+
+class _Unpermute(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, yp, dest, probs):
+        w = None if probs is None else probs.float().contiguous()
+        ctx.save_for_backward(yp, dest, w)
+        ctx.pdtype = None if probs is None else probs.dtype
+        return _combine(yp, dest, w)[0]
+
+    @staticmethod
+    def backward(ctx, dout):
+        yp, dest, w = ctx.saved_tensors
+        R, (T, topk) = yp.shape[0], dest.shape
+        flat = dest.reshape(-1).long()
+        dyp = dw = None
+        if ctx.needs_input_grad[0]:
+            token_of_row = torch.full((R,), -1, dtype=torch.int32, device=yp.device)
+            token_of_row[flat] = (torch.arange(T * topk, device=yp.device) // topk).int()
+            scale = None if w is None else torch.zeros(R, dtype=torch.float32, device=yp.device).scatter_(
+                0, flat, w.reshape(-1))
+            dyp = _gather(dout, token_of_row, scale)
+        if w is not None and ctx.needs_input_grad[2]:
+            dw = _combine(yp, dest, None, dout, want_out=False)[1].to(ctx.pdtype)
+        return dyp, None, dw
+
+
+def moe_permute(x, expert_ids, num_experts):
+    """Sort tokens by expert. ``x [T, H]``, ``expert_ids [T, topk]`` integers in ``[0, num_experts)``. Returns
+    ``(xp, offsets, dest)``: ``xp [R, H]`` in the segment layout of the module docstring, with ``R = round_up(T *
+    topk, 64) + 64 * num_experts`` and every pad and tail row zero; ``offsets`` int32 ``[num_experts + 1]``;
+    ``dest`` int32 ``[T, topk]``, the row of ``xp`` that holds token ``t``'s copy for its ``k``-th expert
+    (``xp[dest[t, k]]`` is bit-equal to ``x[t]``). Differentiable in ``x``; nothing is read on the host."""
+    if x.dim() != 2 or expert_ids.dim() != 2 or expert_ids.shape[0] != x.shape[0]:
+        raise ValueError(f"moe_permute: x [T, H] and expert_ids [T, topk], got {tuple(x.shape)} and "
+                         f"{tuple(expert_ids.shape)}")
+    offsets, dest, token_of_row, _ = _routing_maps(expert_ids, num_experts)
+    return _Permute.apply(x, dest, token_of_row), offsets, dest
+
+
+def moe_unpermute(yp, dest, probs=None):
+    """``out[t] = sum_k probs[t, k] * yp[dest[t, k]]`` for ``yp [R, H]`` and ``dest`` from :func:`moe_permute`;
+    fp32 accumulation in the order ``k = 0, 1, ...``, rounded once. ``probs [T, topk]`` (any float dtype, used in
+    fp32) or None for a plain sum. Differentiable in ``yp`` and ``probs``."""
+    if yp.dim() != 2 or dest.dim() != 2 or (probs is not None and probs.shape != dest.shape):
+        raise ValueError("moe_unpermute: yp [R, H], dest [T, topk] and probs [T, topk] or None")
+    return _Unpermute.apply(yp, dest, probs)

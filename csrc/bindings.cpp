@@ -1986,6 +1986,121 @@ Tensor k_transpose(Tensor x) {
   return out;
 }
 
+// ---------------------------------------------------------------------------
+// Grouped GEMMs over expert segments (gemm_grouped.hip) and the MoE row kernels (moe.hip). `offsets`,
+// `row_of` and `dest` are int32 device tensors and are never read here.
+// ---------------------------------------------------------------------------
+bool grouped_operand_ok(const Tensor& t, const Tensor& like) {
+  return t.device() == like.device() && t.scalar_type() == like.scalar_type() && t.is_contiguous() &&
+         reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+bool grouped_index_ok(const Tensor& t, const Tensor& like) {
+  return t.device() == like.device() && t.scalar_type() == at::kInt && t.is_contiguous();
+}
+
+bool k_gemm_grouped_supported(int64_t R, int64_t K, int64_t N, int64_t E) {
+  return apex::gemm_grouped_supported(R, K, N, E);
+}
+
+// y[seg_e] = x[seg_e] w[e]^T: x [R, K], w [E, N, K], offsets [E + 1] -> y [R, N] (tail rows zero)
+Tensor k_gemm_grouped_nt(Tensor x, Tensor w, Tensor offsets) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && w.dim() == 3 && w.size(2) == x.size(1) &&
+                  (x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf) && grouped_operand_ok(x, x) &&
+                  grouped_operand_ok(w, x) && grouped_index_ok(offsets, x) && offsets.numel() == w.size(0) + 1 &&
+                  apex::gemm_grouped_supported(x.size(0), x.size(1), w.size(1), w.size(0)),
+              "gemm_grouped_nt: unsupported operands");
+  Tensor y = at::empty({x.size(0), w.size(1)}, x.options());
+  apex::GroupedGemmArgs g{};
+  g.A = x.data_ptr();
+  g.B = w.data_ptr();
+  g.C = y.data_ptr();
+  g.offsets = offsets.data_ptr<int>();
+  g.E = (int)w.size(0);
+  g.R = (int)x.size(0);
+  g.N = (int)w.size(1);
+  g.K = (int)x.size(1);
+  check(apex::gemm_grouped_nt(g, dt_code(x.scalar_type()), cur_stream()), "gemm_grouped_nt");
+  return y;
+}
+
+// dw[e] = dy[seg_e]^T x[seg_e]: dy [R, N], x [R, K] -> [E, N, K] in the operand dtype, or, with `acc` (fp32
+// [E, N, K]), added into it (an empty expert's slab is zero / untouched)
+Tensor k_gemm_grouped_tt(Tensor dy, Tensor x, Tensor offsets, const c10::optional<Tensor>& acc) {
+  const int64_t E = offsets.numel() - 1;
+  TORCH_CHECK(dy.is_cuda() && dy.dim() == 2 && x.dim() == 2 && x.size(0) == dy.size(0) &&
+                  (x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf) && grouped_operand_ok(x, x) &&
+                  grouped_operand_ok(dy, x) && grouped_index_ok(offsets, x) &&
+                  apex::gemm_grouped_supported(x.size(0), x.size(1), dy.size(1), E),
+              "gemm_grouped_tt: unsupported operands");
+  apex::GroupedGemmArgs g{};
+  g.A = dy.data_ptr();
+  g.B = x.data_ptr();
+  g.offsets = offsets.data_ptr<int>();
+  g.E = (int)E;
+  g.R = (int)x.size(0);
+  g.N = (int)dy.size(1);
+  g.K = (int)x.size(1);
+  Tensor out;
+  if (has(acc)) {
+    TORCH_CHECK(acc->device() == x.device() && acc->scalar_type() == at::kFloat && acc->is_contiguous() &&
+                    acc->numel() == E * dy.size(1) * x.size(1) && reinterpret_cast<uintptr_t>(acc->data_ptr()) % 16 == 0,
+                "gemm_grouped_tt: acc must be a contiguous, 16-byte aligned fp32 [E, N, K] tensor on x's device");
+    out = *acc;
+    g.acc = out.data_ptr<float>();
+  } else {
+    out = at::empty({E, dy.size(1), x.size(1)}, x.options());
+    g.C = out.data_ptr();
+  }
+  check(apex::gemm_grouped_tt(g, dt_code(x.scalar_type()), cur_stream()), "gemm_grouped_tt");
+  return out;
+}
+
+bool k_moe_rows_supported(Tensor src, int64_t rows) {
+  const auto st = src.scalar_type();
+  return src.is_cuda() && src.dim() == 2 && (st == at::kHalf || st == at::kBFloat16) &&
+         src.size(0) > 0 && apex::moe_rows_supported(rows, src.size(1), dt_code(st));
+}
+
+Tensor k_moe_gather(Tensor src, Tensor row_of, const c10::optional<Tensor>& scale) {
+  const int64_t R = row_of.numel();
+  TORCH_CHECK(k_moe_rows_supported(src, R) && grouped_operand_ok(src, src) && grouped_index_ok(row_of, src),
+              "moe_gather: unsupported operands");
+  if (has(scale))
+    TORCH_CHECK(scale->device() == src.device() && scale->scalar_type() == at::kFloat && scale->is_contiguous() &&
+                    scale->numel() == R,
+                "moe_gather: scale must be a contiguous fp32 [R] tensor on src's device");
+  Tensor out = at::empty({R, src.size(1)}, src.options());
+  check(apex::moe_gather(src.data_ptr(), row_of.data_ptr<int>(), opt_ptr<float>(scale), out.data_ptr(), (int)R,
+                         (int)src.size(0), (int)src.size(1), dt_code(src.scalar_type()), cur_stream()),
+        "moe_gather");
+  return out;
+}
+
+// (out [T, H] or None when !want_out, dw [T, topk] fp32 or None when g is None)
+std::vector<c10::optional<Tensor>> k_moe_combine(Tensor src, Tensor dest, const c10::optional<Tensor>& w,
+                                                 const c10::optional<Tensor>& g, bool want_out) {
+  TORCH_CHECK(dest.dim() == 2 && k_moe_rows_supported(src, dest.size(0)) && grouped_operand_ok(src, src) &&
+                  grouped_index_ok(dest, src) && dest.size(1) >= 1 && dest.size(1) <= apex::kMoeMaxTopk &&
+                  (want_out || has(g)),
+              "moe_combine: unsupported operands");
+  const int64_t T = dest.size(0), topk = dest.size(1), H = src.size(1);
+  if (has(w))
+    TORCH_CHECK(w->device() == src.device() && w->scalar_type() == at::kFloat && w->is_contiguous() &&
+                    w->numel() == T * topk,
+                "moe_combine: w must be a contiguous fp32 [T, topk] tensor on src's device");
+  if (has(g))
+    TORCH_CHECK(grouped_operand_ok(*g, src) && g->dim() == 2 && g->size(0) == T && g->size(1) == H,
+                "moe_combine: g must be a contiguous, 16-byte aligned [T, H] tensor of src's dtype and device");
+  c10::optional<Tensor> out, dw;
+  if (want_out) out = at::empty({T, H}, src.options());
+  if (has(g)) dw = at::empty({T, topk}, src.options().dtype(at::kFloat));
+  check(apex::moe_combine(src.data_ptr(), dest.data_ptr<int>(), opt_ptr<float>(w), has(g) ? g->data_ptr() : nullptr,
+                          want_out ? out->data_ptr() : nullptr, has(g) ? dw->data_ptr<float>() : nullptr, (int)T,
+                          (int)topk, (int)src.size(0), (int)H, dt_code(src.scalar_type()), cur_stream()),
+        "moe_combine");
+  return {out, dw};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -2123,6 +2238,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_tt", &k_gemm_tt, py::arg("a"), py::arg("b"), py::arg("splits"), py::arg("out_dtype"),
         py::arg("out") = py::none());
   m.def("gemm_tt_acc", &k_gemm_tt_acc);
+  m.def("gemm_grouped_supported", &k_gemm_grouped_supported);
+  m.def("gemm_grouped_nt", &k_gemm_grouped_nt);
+  m.def("gemm_grouped_tt", &k_gemm_grouped_tt, py::arg("dy"), py::arg("x"), py::arg("offsets"),
+        py::arg("acc") = py::none());
+  m.def("moe_rows_supported", &k_moe_rows_supported);
+  m.def("moe_gather", &k_moe_gather, py::arg("src"), py::arg("row_of"), py::arg("scale") = py::none());
+  m.def("moe_combine", &k_moe_combine, py::arg("src"), py::arg("dest"), py::arg("w") = py::none(),
+        py::arg("g") = py::none(), py::arg("want_out") = true);
   m.def("gemm_tt_f8_supported", &k_gemm_tt_f8_supported);
   m.def("gemm_tt_f8", &k_gemm_tt_f8, py::arg("a"), py::arg("b"), py::arg("alpha_a"), py::arg("alpha_b"),
         py::arg("fmt_a"), py::arg("fmt_b"), py::arg("splits"), py::arg("out_dtype"), py::arg("out") = py::none());

@@ -377,6 +377,33 @@ int gemm_mx4(const MxGemmArgs& g, int out_dt, hipStream_t s);
 int gemm_bias_grad(const float* part, int parts, int N, void* out, int odt, hipStream_t s);
 int transpose_2d(const void* in, void* out, int R, int C, int dt, hipStream_t s);
 
+// ----------------------------- grouped GEMM (gemm_grouped.hip) -------------
+// Expert-sorted rows [R, *] cut into E segments by `offsets` (int32 [E + 1] on the device, multiples of 64,
+// never read on the host; the layout is described at the top of gemm_grouped.hip).
+struct GroupedGemmArgs {
+  const void* A;       // nt: X [R, K]            tt: dY [R, N]
+  const void* B;       // nt: W [E, N, K]         tt: X [R, K]
+  void* C;             // nt: Y [R, N]            tt: dW [E, N, K] in the operand dtype, or null
+  float* acc;          //                         tt: fp32 [E, N, K] accumulator (+=), or null
+  const int* offsets;  // [E + 1]
+  int E, R, N, K;
+};
+bool gemm_grouped_supported(int64_t R, int64_t K, int64_t N, int64_t E);
+int gemm_grouped_nt(const GroupedGemmArgs& g, int dt, hipStream_t s);
+int gemm_grouped_tt(const GroupedGemmArgs& g, int dt, hipStream_t s);
+
+// ----------------------------- MoE token movement (moe.hip) ----------------
+constexpr int kMoeMaxTopk = 8;
+// bf16 / fp16 rows of H elements moved in 16-byte chunks: H % 8 == 0
+bool moe_rows_supported(int64_t rows, int64_t H, int dt);
+// out[r, :] = scale[r] * src[row_of[r], :] for r < R (src [S, H]); row_of[r] < 0: zeros; scale may be null
+int moe_gather(const void* src, const int* row_of, const float* scale, void* out, int R, int S, int H, int dt,
+               hipStream_t s);
+// out[t, :] = sum_k w[t, k] * src[dest[t, k], :] (src [R, H], w fp32 or null, out may be null) and, with g [Tn, H],
+// dw[t, k] = <g[t, :], src[dest[t, k], :]>; topk <= kMoeMaxTopk
+int moe_combine(const void* src, const int* dest, const float* w, const void* g, void* out, float* dw, int Tn, int topk,
+                int R, int H, int dt, hipStream_t s);
+
 // ----------------------------- input pipeline (K-09) -----------------------
 // layout: 0 NHWC->NHWC, 1 NHWC->NCHW (hw % 8 == 0, C in {1,3,4}), 2 NCHW->NCHW. Returns 1 if
 // the geometry is unsupported.
