@@ -59,6 +59,7 @@ class MegatronGPTConfig:
     # instead of dense_h_to_4h / dense_4h_to_h) with this many experts; tensor-parallel size 1 only
     num_moe_experts: int | None = None
     moe_router_topk: int = 2
+    moe_aux_loss_coeff: float = 0.0  # load-balancing loss of every MoE layer (its gradient rides the layer's output)
 
     def __post_init__(self):
         if self.activation not in _ACTIVATIONS:
@@ -124,7 +125,8 @@ class ParallelTransformerLayer(nn.Module):
                 raise ValueError("num_moe_experts needs a tensor-parallel world size of 1 (experts are not sharded), "
                                  f"got {tpws}")
             self.mlp = MoEMLP(c.hidden_size, c.ffn_hidden_size, c.num_moe_experts, c.moe_router_topk, c.activation,
-                              init_std=c.init_method_std, out_std=out_std, params_dtype=c.params_dtype)
+                              init_std=c.init_method_std, out_std=out_std, params_dtype=c.params_dtype,
+                              aux_loss_coeff=c.moe_aux_loss_coeff)
             return
         if self.gated_act is not None and c.ffn_hidden_size % tpws:
             raise ValueError(f"ffn_hidden_size={c.ffn_hidden_size} must be a multiple of the tensor-parallel "

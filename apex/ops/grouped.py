@@ -9,15 +9,18 @@ routing, and ``offsets`` is never read on the host: there is no sync, and everyt
 a ``torch.cuda.graph``.
 
   grouped_linear(x, weight, offsets)         y[seg_e] = x[seg_e] @ weight[e].T,  weight [E, N, K], no bias
+  moe_route(logits, topk, aux_loss)          router logits [T, E] -> gate, expert ids, row maps, aux loss
   moe_permute(x, expert_ids, num_experts)    tokens [T, H] -> (xp [R, H], offsets, dest [T, topk])
   moe_unpermute(yp, dest, probs)             out[t] = sum_k probs[t, k] * yp[dest[t, k]]
 
 Device tensors in bf16 / fp16 run on the HIP kernels of csrc/gemm_grouped.hip (one launch per GEMM: forward,
-input gradient, weight gradient) and csrc/moe.hip. CPU tensors, ``APEX_FORCE_REFERENCE=1`` and the shapes
+input gradient, weight gradient), csrc/moe.hip and csrc/moe_route.hip (routing and row maps). CPU tensors, ``APEX_FORCE_REFERENCE=1`` and the shapes
 ``grouped_gemm_supported`` declines take the PyTorch formulation below, which keeps the same contract (zero
 pads, zero tail, no host read of ``offsets``).
 """
 from __future__ import annotations
+
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -175,6 +178,113 @@ def _routing_maps(expert_ids, num_experts):
     return offsets.int(), dest.view(T, topk), token_of_row, R
 
 
+def _native_maps(expert_ids, num_experts):
+    return (_ext.use_native(expert_ids) and expert_ids.dtype in (torch.int32, torch.int64)
+            and expert_ids.is_contiguous() and expert_ids.numel() > 0
+            and _ext.require().moe_route_supported(expert_ids.shape[0], num_experts, expert_ids.shape[1], torch.float32))
+
+
+def _maps(expert_ids, num_experts):
+    """(offsets, dest, token_of_row) of ``_routing_maps``, on supported device ids by the hist, scan and place
+    kernels of csrc/moe_route.hip instead of the sort: the same tensors, bit for bit."""
+    if _native_maps(expert_ids, num_experts):
+        return tuple(_ext.require().moe_route_maps(expert_ids, num_experts)[:3])
+    return _routing_maps(expert_ids, num_experts)[:3]
+
+
+# ---------------------------------------------------------------------------
+# routing
+class Routing(NamedTuple):
+    """What :func:`moe_route` returns. ``R = round_up(T * topk, 64) + 64 * E``."""
+    probs: torch.Tensor               # fp32 [T, topk]: softmax over the chosen logits, descending
+    expert_ids: torch.Tensor          # int32 [T, topk]
+    tokens_per_expert: torch.Tensor   # int32 [E]
+    offsets: torch.Tensor             # int32 [E + 1], the segment table of the module docstring
+    dest: torch.Tensor                # int32 [T, topk]: the row of token t's copy for its k-th expert
+    token_of_row: torch.Tensor        # int32 [R]: the token of every row, -1 on pad and tail rows
+    row_prob: torch.Tensor            # fp32 [R]: probs[t, k] at dest[t, k], 0 elsewhere (detached)
+    aux_loss: Optional[torch.Tensor]  # 0-dim fp32, or None
+
+
+def moe_route_supported(T, E, topk, dtype):
+    """Can the routing kernels take ``[T, E]`` logits of ``dtype``? fp32 / fp16 / bf16, ``1 <= topk <= 8``, ``topk
+    <= E <= 256``, ``T >= 1`` and ``T * topk + 64 * E < 2**31``. Needs the built extension."""
+    return bool(_ext.require().moe_route_supported(int(T), int(E), int(topk), dtype))
+
+
+def _aux_scale(T, E, topk):
+    return E / (T * T * topk)
+
+
+def _route_reference(logits, topk, aux_loss):
+    """The PyTorch formulation: a stable descending sort (ties to the lowest expert index), a softmax over the
+    first ``topk`` columns, ``_routing_maps``."""
+    T, E = logits.shape
+    lf = logits.float()
+    top, idx = torch.sort(lf, dim=-1, descending=True, stable=True)
+    ids = idx[:, :topk].contiguous()
+    probs = torch.softmax(top[:, :topk], dim=-1)
+    offsets, dest, token_of_row, R = _routing_maps(ids, E)
+    flat = ids.reshape(-1)
+    counts = torch.zeros(E, dtype=torch.long, device=ids.device).scatter_add_(0, flat, torch.ones_like(flat))
+    row_prob = torch.zeros(R, dtype=torch.float32, device=ids.device).scatter_(
+        0, dest.reshape(-1).long(), probs.detach().reshape(-1))
+    aux = None
+    if aux_loss:
+        aux = _aux_scale(T, E, topk) * (counts.float() * torch.softmax(lf, dim=-1).sum(0)).sum()
+    return Routing(probs, ids.int(), counts.int(), offsets, dest, token_of_row, row_prob, aux)
+
+
+class _Route(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, topk, aux_loss):
+        probs, ids, counts, offsets, dest, token_of_row, row_prob, aux = _ext.require().moe_route_fwd(
+            logits, topk, aux_loss)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(logits, ids, probs, counts)
+        ctx.mark_non_differentiable(ids, counts, offsets, dest, token_of_row, row_prob)
+        return probs, ids, counts, offsets, dest, token_of_row, row_prob, aux   # aux: None without aux_loss
+
+    @staticmethod
+    def backward(ctx, dprobs, *rest):
+        logits, ids, probs, counts = ctx.saved_tensors
+        d_aux = rest[-1]
+        if dprobs is not None:
+            dprobs = dprobs.float().contiguous()
+        if d_aux is not None:
+            d_aux = d_aux.float().reshape(1).contiguous()
+        return _ext.require().moe_route_bwd(logits, ids, probs, dprobs, counts, d_aux), None, None
+
+
+def moe_route(logits, topk, aux_loss=False, fused=None):
+    """Route tokens to their ``topk`` experts. ``logits [T, E]`` (fp32, fp16 or bf16; used in fp32). Returns a
+    :class:`Routing`: ``expert_ids`` are the ``topk`` largest logits of every token in descending order, equal
+    logits going to the lowest expert index; ``probs`` the softmax over those ``topk`` logits; ``offsets``,
+    ``dest`` and ``token_of_row`` the row maps :func:`moe_permute` builds for these ids, so passing the routing
+    to it and to :func:`moe_unpermute` launches no index op. With ``aux_loss`` the Switch / Megatron
+    load-balancing loss with coefficient 1, ``E / (T * T * topk) * sum_e tokens_per_expert[e] * sum_t
+    softmax(logits)[t, e]``, the counts being constants of its gradient. Differentiable in ``logits`` through
+    ``probs`` and ``aux_loss``.
+
+    Device logits within ``moe_route_supported`` run csrc/moe_route.hip: three launches forward, one backward,
+    no atomics, nothing read on the host, bit-reproducible. CPU tensors, ``APEX_FORCE_REFERENCE=1`` and other
+    shapes take a stable sort in PyTorch with the same outputs. ``fused``: None takes the kernels where they
+    were measured faster (``E < 64`` or ``topk <= 2``), True insists on them, False on the PyTorch path."""
+    if logits.dim() != 2 or not 1 <= topk <= logits.shape[1]:
+        raise ValueError(f"moe_route: logits [T, E] and 1 <= topk <= E, got {tuple(logits.shape)} and topk={topk}")
+    native = _ext.use_native(logits) and logits.dtype in (torch.float32,) + _HALF and logits.numel() > 0 \
+        and moe_route_supported(logits.shape[0], logits.shape[1], topk, logits.dtype)
+    if fused and not native:
+        raise ValueError("moe_route: fused=True needs device logits within moe_route_supported")
+    if fused is None:
+        # profiles/moe_route_vs_torch.jsonl: with one token per wave pass (E >= 64) the kernels lose to the
+        # PyTorch formulation at topk = 8 and win at topk = 2; nothing between was measured
+        fused = native and (logits.shape[1] < 64 or topk <= 2)
+    if fused:
+        return Routing(*_Route.apply(logits.contiguous(), int(topk), bool(aux_loss)))
+    return _route_reference(logits, int(topk), bool(aux_loss))
+
+
 class _Permute(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, dest, token_of_row):
@@ -189,46 +299,59 @@ class _Permute(torch.autograd.Function):
 
 class _Unpermute(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, yp, dest, probs):
+    def forward(ctx, yp, dest, probs, token_of_row, row_prob):
         w = None if probs is None else probs.float().contiguous()
-        ctx.save_for_backward(yp, dest, w)
+        ctx.save_for_backward(yp, dest, w, token_of_row, row_prob)
         ctx.pdtype = None if probs is None else probs.dtype
         return _combine(yp, dest, w)[0]
 
     @staticmethod
     def backward(ctx, dout):
-        yp, dest, w = ctx.saved_tensors
+        yp, dest, w, token_of_row, scale = ctx.saved_tensors
         R, (T, topk) = yp.shape[0], dest.shape
-        flat = dest.reshape(-1).long()
         dyp = dw = None
         if ctx.needs_input_grad[0]:
-            token_of_row = torch.full((R,), -1, dtype=torch.int32, device=yp.device)
-            token_of_row[flat] = (torch.arange(T * topk, device=yp.device) // topk).int()
-            scale = None if w is None else torch.zeros(R, dtype=torch.float32, device=yp.device).scatter_(
-                0, flat, w.reshape(-1))
+            if token_of_row is None:   # no routing given: rebuild the row maps from dest
+                flat = dest.reshape(-1).long()
+                token_of_row = torch.full((R,), -1, dtype=torch.int32, device=yp.device)
+                token_of_row[flat] = (torch.arange(T * topk, device=yp.device) // topk).int()
+                scale = None if w is None else torch.zeros(R, dtype=torch.float32, device=yp.device).scatter_(
+                    0, flat, w.reshape(-1))
             dyp = _gather(dout, token_of_row, scale)
         if w is not None and ctx.needs_input_grad[2]:
             dw = _combine(yp, dest, None, dout, want_out=False)[1].to(ctx.pdtype)
-        return dyp, None, dw
+        return dyp, None, dw, None, None
 
 
-def moe_permute(x, expert_ids, num_experts):
+def moe_permute(x, expert_ids, num_experts, routing=None):
     """Sort tokens by expert. ``x [T, H]``, ``expert_ids [T, topk]`` integers in ``[0, num_experts)``. Returns
-    ``(xp, offsets, dest)``: ``xp [R, H]`` in the segment layout of the module docstring, with ``R = round_up(T *
-    topk, 64) + 64 * num_experts`` and every pad and tail row zero; ``offsets`` int32 ``[num_experts + 1]``;
-    ``dest`` int32 ``[T, topk]``, the row of ``xp`` that holds token ``t``'s copy for its ``k``-th expert
-    (``xp[dest[t, k]]`` is bit-equal to ``x[t]``). Differentiable in ``x``; nothing is read on the host."""
+    ``(xp, offsets, dest)``: ``xp [R, H]`` in the segment layout of the module docstring, with ``R = round_up(T * topk, 64) + 64 * num_experts`` and every pad and tail row zero;
+    ``offsets`` int32 ``[num_experts + 1]``; ``dest`` int32 ``[T, topk]``, the row of ``xp`` that holds token
+    ``t``'s copy for its ``k``-th expert (``xp[dest[t, k]]`` is bit-equal to ``x[t]``). Differentiable in ``x``;
+    nothing is read on the host. ``routing``: the :class:`Routing` that :func:`moe_route` returned with these
+    ``expert_ids``; its maps are used as they are and no index op is launched."""
     if x.dim() != 2 or expert_ids.dim() != 2 or expert_ids.shape[0] != x.shape[0]:
         raise ValueError(f"moe_permute: x [T, H] and expert_ids [T, topk], got {tuple(x.shape)} and "
                          f"{tuple(expert_ids.shape)}")
-    offsets, dest, token_of_row, _ = _routing_maps(expert_ids, num_experts)
+    if routing is not None:
+        if routing.dest.shape != expert_ids.shape or routing.offsets.numel() != num_experts + 1:
+            raise ValueError("moe_permute: routing does not belong to these expert_ids")
+        offsets, dest, token_of_row = routing.offsets, routing.dest, routing.token_of_row
+    else:
+        offsets, dest, token_of_row = _maps(expert_ids, num_experts)
     return _Permute.apply(x, dest, token_of_row), offsets, dest
 
 
-def moe_unpermute(yp, dest, probs=None):
+def moe_unpermute(yp, dest, probs=None, routing=None):
     """``out[t] = sum_k probs[t, k] * yp[dest[t, k]]`` for ``yp [R, H]`` and ``dest`` from :func:`moe_permute`;
     fp32 accumulation in the order ``k = 0, 1, ...``, rounded once. ``probs [T, topk]`` (any float dtype, used in
-    fp32) or None for a plain sum. Differentiable in ``yp`` and ``probs``."""
+    fp32) or None for a plain sum. Differentiable in ``yp`` and ``probs``. ``routing``: the :class:`Routing`
+    that ``dest`` and ``probs`` (its ``probs``, or None) come from; the backward then reads its ``token_of_row``
+    and ``row_prob`` instead of rebuilding them from ``dest``."""
     if yp.dim() != 2 or dest.dim() != 2 or (probs is not None and probs.shape != dest.shape):
         raise ValueError("moe_unpermute: yp [R, H], dest [T, topk] and probs [T, topk] or None")
-    return _Unpermute.apply(yp, dest, probs)
+    if routing is None:
+        return _Unpermute.apply(yp, dest, probs, None, None)
+    if routing.token_of_row.numel() != yp.shape[0]:
+        raise ValueError("moe_unpermute: routing does not belong to yp")
+    return _Unpermute.apply(yp, dest, probs, routing.token_of_row, None if probs is None else routing.row_prob)

@@ -2101,6 +2101,107 @@ std::vector<c10::optional<Tensor>> k_moe_combine(Tensor src, Tensor dest, const 
   return {out, dw};
 }
 
+// ---------------------------------------------------------------------------
+// MoE routing (moe_route.hip): three launches forward, one backward, nothing read on the host.
+// ---------------------------------------------------------------------------
+bool k_moe_route_supported(int64_t T, int64_t E, int64_t topk, at::ScalarType dt) {
+  return (dt == at::kFloat || dt == at::kHalf || dt == at::kBFloat16) &&
+         apex::moe_route_supported(T, E, topk, dt_code(dt));
+}
+
+// Allocates the outputs and the work buffers of one routing of T tokens and fills in `a`; returns
+// {expert_ids, tokens_per_expert, offsets, dest, token_of_row} and keeps the work buffers alive in `work`.
+std::vector<Tensor> route_alloc(apex::MoeRouteArgs& a, int64_t T, int64_t E, int64_t topk, bool aux,
+                                const at::TensorOptions& dev, std::vector<Tensor>& work) {
+  const int64_t NB = (T + 255) / 256, R = (T * topk + 63) / 64 * 64 + 64 * E;
+  const auto io = dev.dtype(at::kInt), fo = dev.dtype(at::kFloat);
+  Tensor ids = at::empty({T, topk}, io), tpe = at::empty({E}, io), offsets = at::empty({E + 1}, io),
+         dest = at::empty({T, topk}, io), tor = at::empty({R}, io);
+  work = {at::empty({T, topk}, io), at::empty({NB, E}, io), at::empty({NB, E}, io)};
+  if (aux) work.push_back(at::empty({NB, E}, fo));
+  a.T = (int)T, a.E = (int)E, a.topk = (int)topk, a.R = (int)R;
+  a.expert_ids = ids.data_ptr<int>();
+  a.rank = work[0].data_ptr<int>();
+  a.block_counts = work[1].data_ptr<int>();
+  a.block_base = work[2].data_ptr<int>();
+  a.block_psum = aux ? work[3].data_ptr<float>() : nullptr;
+  a.tokens_per_expert = tpe.data_ptr<int>();
+  a.offsets = offsets.data_ptr<int>();
+  a.dest = dest.data_ptr<int>();
+  a.token_of_row = tor.data_ptr<int>();
+  return {ids, tpe, offsets, dest, tor};
+}
+
+// logits [T, E] -> (probs, expert_ids, tokens_per_expert, offsets, dest, token_of_row, row_prob, aux or None)
+std::vector<c10::optional<Tensor>> k_moe_route_fwd(Tensor logits, int64_t topk, bool aux) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.is_contiguous() &&
+                  k_moe_route_supported(logits.size(0), logits.size(1), topk, logits.scalar_type()),
+              "moe_route_fwd: unsupported operands");
+  const int64_t T = logits.size(0), E = logits.size(1);
+  apex::MoeRouteArgs a{};
+  std::vector<Tensor> work;
+  auto out = route_alloc(a, T, E, topk, aux, logits.options(), work);
+  const auto fo = logits.options().dtype(at::kFloat);
+  Tensor probs = at::empty({T, topk}, fo), row_prob = at::empty({(int64_t)a.R}, fo);
+  c10::optional<Tensor> aux_t;
+  if (aux) aux_t = at::empty({}, fo);
+  a.logits = logits.data_ptr();
+  a.probs = probs.data_ptr<float>();
+  a.row_prob = row_prob.data_ptr<float>();
+  a.aux = aux ? aux_t->data_ptr<float>() : nullptr;
+  hipStream_t s = cur_stream();
+  check(apex::moe_route_topk(a, dt_code(logits.scalar_type()), s), "moe_route_topk");
+  check(apex::moe_route_scan(a, s), "moe_route_scan");
+  check(apex::moe_route_place(a, s), "moe_route_place");
+  return {probs, out[0], out[1], out[2], out[3], out[4], row_prob, aux_t};
+}
+
+// expert_ids [T, topk] (int32 / int64) -> (offsets, dest, token_of_row, tokens_per_expert)
+std::vector<Tensor> k_moe_route_maps(Tensor expert_ids, int64_t E) {
+  const auto st = expert_ids.scalar_type();
+  TORCH_CHECK(expert_ids.is_cuda() && expert_ids.dim() == 2 && expert_ids.is_contiguous() &&
+                  (st == at::kInt || st == at::kLong) &&
+                  k_moe_route_supported(expert_ids.size(0), E, expert_ids.size(1), at::kFloat),
+              "moe_route_maps: unsupported operands");
+  apex::MoeRouteArgs a{};
+  std::vector<Tensor> work;
+  auto out = route_alloc(a, expert_ids.size(0), E, expert_ids.size(1), false, expert_ids.options(), work);
+  a.ids_in = expert_ids.data_ptr();
+  hipStream_t s = cur_stream();
+  check(apex::moe_route_hist(a, st == at::kLong, s), "moe_route_hist");
+  check(apex::moe_route_scan(a, s), "moe_route_scan");
+  check(apex::moe_route_place(a, s), "moe_route_place");
+  return {out[2], out[3], out[4], out[1]};
+}
+
+Tensor k_moe_route_bwd(Tensor logits, Tensor expert_ids, Tensor probs, const c10::optional<Tensor>& dprobs,
+                       Tensor tokens_per_expert, const c10::optional<Tensor>& d_aux) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.is_contiguous() && expert_ids.dim() == 2 &&
+                  expert_ids.size(0) == logits.size(0) && grouped_index_ok(expert_ids, expert_ids) &&
+                  expert_ids.device() == logits.device() &&
+                  k_moe_route_supported(logits.size(0), logits.size(1), expert_ids.size(1), logits.scalar_type()),
+              "moe_route_bwd: unsupported operands");
+  const int64_t T = logits.size(0), E = logits.size(1), topk = expert_ids.size(1);
+  auto f32_ok = [&](const Tensor& t, int64_t n) {
+    return t.device() == logits.device() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == n;
+  };
+  TORCH_CHECK(f32_ok(probs, T * topk) && (!has(dprobs) || f32_ok(*dprobs, T * topk)) && (!has(d_aux) || f32_ok(*d_aux, 1)),
+              "moe_route_bwd: probs, dprobs [T, topk] and d_aux [1] must be contiguous fp32 tensors on logits' device");
+  TORCH_CHECK(grouped_index_ok(tokens_per_expert, expert_ids) && tokens_per_expert.numel() == E,
+              "moe_route_bwd: tokens_per_expert must be an int32 [E] tensor on logits' device");
+  apex::MoeRouteArgs a{};
+  a.T = (int)T, a.E = (int)E, a.topk = (int)topk, a.R = (int)((T * topk + 63) / 64 * 64 + 64 * E);
+  a.logits = logits.data_ptr();
+  a.expert_ids = expert_ids.data_ptr<int>();
+  a.probs = probs.data_ptr<float>();
+  a.tokens_per_expert = tokens_per_expert.data_ptr<int>();
+  Tensor dlogits = at::empty_like(logits);
+  check(apex::moe_route_bwd(a, opt_ptr<float>(dprobs), opt_ptr<float>(d_aux), dlogits.data_ptr(),
+                            dt_code(logits.scalar_type()), cur_stream()),
+        "moe_route_bwd");
+  return dlogits;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -2246,6 +2347,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_gather", &k_moe_gather, py::arg("src"), py::arg("row_of"), py::arg("scale") = py::none());
   m.def("moe_combine", &k_moe_combine, py::arg("src"), py::arg("dest"), py::arg("w") = py::none(),
         py::arg("g") = py::none(), py::arg("want_out") = true);
+  m.def("moe_route_supported", &k_moe_route_supported);
+  m.def("moe_route_fwd", &k_moe_route_fwd, py::arg("logits"), py::arg("topk"), py::arg("aux") = false);
+  m.def("moe_route_maps", &k_moe_route_maps);
+  m.def("moe_route_bwd", &k_moe_route_bwd);
   m.def("gemm_tt_f8_supported", &k_gemm_tt_f8_supported);
   m.def("gemm_tt_f8", &k_gemm_tt_f8, py::arg("a"), py::arg("b"), py::arg("alpha_a"), py::arg("alpha_b"),
         py::arg("fmt_a"), py::arg("fmt_b"), py::arg("splits"), py::arg("out_dtype"), py::arg("out") = py::none());

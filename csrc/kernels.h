@@ -404,6 +404,37 @@ int moe_gather(const void* src, const int* row_of, const float* scale, void* out
 int moe_combine(const void* src, const int* dest, const float* w, const void* g, void* out, float* dw, int Tn, int topk,
                 int R, int H, int dt, hipStream_t s);
 
+// ----------------------------- MoE routing (moe_route.hip) -----------------
+// Router logits [T, E] -> gate, expert ids and the row maps of the expert-sorted layout. Forward is topk (or
+// hist, from given ids), scan, place on one stream; R = round_up(T * topk, 64) + 64 * E. Nullable: logits /
+// ids_in (one of them), probs and row_prob (hist path), block_psum and aux (both or neither: the aux loss).
+struct MoeRouteArgs {
+  const void* logits;      // [T, E] fp32 / fp16 / bf16
+  const void* ids_in;      // [T, topk] int32 / int64 (hist)
+  int T, E, topk, R;
+  int* expert_ids;         // [T, topk], every entry in [0, E)
+  float* probs;            // [T, topk] gate
+  int* rank;               // [T, topk] work
+  int* block_counts;       // [NB, E] work, NB = ceil(T / 256)
+  float* block_psum;       // [NB, E] work
+  int* block_base;         // [NB, E] work
+  int* tokens_per_expert;  // [E]
+  int* offsets;            // [E + 1]
+  float* aux;              // [1]: E / (T T topk) sum_e tokens_per_expert[e] * sum_t softmax(logits)[t, e]
+  int* dest;               // [T, topk]
+  int* token_of_row;       // [R], -1 on pad and tail rows
+  float* row_prob;         // [R], 0 on pad and tail rows
+};
+// 1 <= topk <= kMoeMaxTopk, topk <= E <= 256, T >= 1, T * topk + 64 * E < 2^31
+bool moe_route_supported(int64_t T, int64_t E, int64_t topk, int dt);
+int moe_route_topk(const MoeRouteArgs& a, int dt, hipStream_t s);
+int moe_route_hist(const MoeRouteArgs& a, bool ids_i64, hipStream_t s);
+int moe_route_scan(const MoeRouteArgs& a, hipStream_t s);
+int moe_route_place(const MoeRouteArgs& a, hipStream_t s);
+// dlogits [T, E] in the logits' dtype from dprobs [T, topk] and the device scalar d_aux (either may be null)
+int moe_route_bwd(const MoeRouteArgs& a, const float* dprobs, const float* d_aux, void* dlogits, int dt,
+                  hipStream_t s);
+
 // ----------------------------- input pipeline (K-09) -----------------------
 // layout: 0 NHWC->NHWC, 1 NHWC->NCHW (hw % 8 == 0, C in {1,3,4}), 2 NCHW->NCHW. Returns 1 if
 // the geometry is unsupported.
