@@ -60,6 +60,13 @@ class MegatronGPTConfig:
     num_moe_experts: int | None = None
     moe_router_topk: int = 2
     moe_aux_loss_coeff: float = 0.0  # load-balancing loss of every MoE layer (its gradient rides the layer's output)
+    # the router (apex.ops.moe_route): "sigmoid" takes the four options below, "softmax" none of them
+    moe_router_score_function: str = "softmax"
+    moe_router_num_groups: int | None = None       # group-limited selection: experts in this many groups,
+    moe_router_group_topk: int | None = None       # chosen from the best this many of them
+    moe_router_topk_scaling_factor: float = 1.0    # the normalised gate times this
+    moe_router_enable_expert_bias: bool = False    # aux-loss-free balancing: a selection bias per expert,
+    moe_router_bias_update_rate: float = 1e-3      # moved by this much per MegatronGPT.update_expert_bias()
 
     def __post_init__(self):
         if self.activation not in _ACTIVATIONS:
@@ -126,7 +133,10 @@ class ParallelTransformerLayer(nn.Module):
                                  f"got {tpws}")
             self.mlp = MoEMLP(c.hidden_size, c.ffn_hidden_size, c.num_moe_experts, c.moe_router_topk, c.activation,
                               init_std=c.init_method_std, out_std=out_std, params_dtype=c.params_dtype,
-                              aux_loss_coeff=c.moe_aux_loss_coeff)
+                              aux_loss_coeff=c.moe_aux_loss_coeff, score_function=c.moe_router_score_function,
+                              num_groups=c.moe_router_num_groups, group_topk=c.moe_router_group_topk,
+                              scaling_factor=c.moe_router_topk_scaling_factor,
+                              expert_bias=c.moe_router_enable_expert_bias)
             return
         if self.gated_act is not None and c.ffn_hidden_size % tpws:
             raise ValueError(f"ffn_hidden_size={c.ffn_hidden_size} must be a multiple of the tensor-parallel "
@@ -256,6 +266,14 @@ class MegatronGPT(nn.Module):
 
     def set_input_tensor(self, input_tensor):
         self.input_tensor = input_tensor
+
+    def update_expert_bias(self):
+        """With ``moe_router_enable_expert_bias``: one balancing step of every MoE layer's selection bias by
+        ``moe_router_bias_update_rate``, from the token counts of the forwards since the last call. Call it
+        once per optimizer step."""
+        for layer in self.layers:
+            if layer.mlp is not None and layer.mlp.expert_bias is not None:
+                layer.mlp.update_expert_bias(self.config.moe_router_bias_update_rate)
 
     def forward(self, input_ids, labels=None):
         if self.pre_process:

@@ -196,7 +196,7 @@ def _maps(expert_ids, num_experts):
 # routing
 class Routing(NamedTuple):
     """What :func:`moe_route` returns. ``R = round_up(T * topk, 64) + 64 * E``."""
-    probs: torch.Tensor               # fp32 [T, topk]: softmax over the chosen logits, descending
+    probs: torch.Tensor               # fp32 [T, topk]: softmax over the chosen logits, descending (sigmoid: rule 5)
     expert_ids: torch.Tensor          # int32 [T, topk]
     tokens_per_expert: torch.Tensor   # int32 [E]
     offsets: torch.Tensor             # int32 [E + 1], the segment table of the module docstring
@@ -235,13 +235,43 @@ def _route_reference(logits, topk, aux_loss):
     return Routing(probs, ids.int(), counts.int(), offsets, dest, token_of_row, row_prob, aux)
 
 
+def _sigmoid_reference(logits, topk, aux_loss, expert_bias, num_groups, group_topk, scaling_factor):
+    """The PyTorch formulation of the sigmoid router (the seven rules of :func:`moe_route`): stable descending
+    sorts for the groups and the experts, so ties go to the lowest index; nothing is read on the host."""
+    T, E = logits.shape
+    lf = logits.float()
+    s = torch.sigmoid(torch.where(lf != lf, torch.full_like(lf, float("-inf")), lf))
+    key = s.detach() if expert_bias is None else s.detach() + expert_bias.float()
+    if num_groups:
+        top2 = key.view(T, num_groups, E // num_groups).topk(2, dim=-1).values
+        kept = torch.sort(top2[..., 0] + top2[..., 1], dim=-1, descending=True, stable=True).indices[:, :group_topk]
+        mask = torch.zeros(T, num_groups, dtype=torch.bool, device=key.device).scatter_(1, kept, True)
+        key = key.masked_fill(~mask.repeat_interleave(E // num_groups, dim=1), float("-inf"))
+    ids = torch.sort(key, dim=-1, descending=True, stable=True).indices[:, :topk].contiguous()
+    probs = scaling_factor * s.gather(1, ids)
+    if topk > 1:
+        probs = probs / (s.gather(1, ids).sum(-1, keepdim=True) + 1e-20)
+    offsets, dest, token_of_row, R = _routing_maps(ids, E)
+    flat = ids.reshape(-1)
+    counts = torch.zeros(E, dtype=torch.long, device=ids.device).scatter_add_(0, flat, torch.ones_like(flat))
+    row_prob = torch.zeros(R, dtype=torch.float32, device=ids.device).scatter_(
+        0, dest.reshape(-1).long(), probs.detach().reshape(-1))
+    aux = None
+    if aux_loss:
+        aux = _aux_scale(T, E, topk) * (counts.float() * (s / (s.sum(-1, keepdim=True) + 1e-20)).sum(0)).sum()
+    return Routing(probs, ids.int(), counts.int(), offsets, dest, token_of_row, row_prob, aux)
+
+
 class _Route(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, topk, aux_loss):
+    def forward(ctx, logits, topk, aux_loss, score_function="softmax", expert_bias=None, num_groups=0, group_topk=0,
+                scaling_factor=1.0):
         probs, ids, counts, offsets, dest, token_of_row, row_prob, aux = _ext.require().moe_route_fwd(
-            logits, topk, aux_loss)
+            logits, topk, aux_loss, score_function=score_function, expert_bias=expert_bias, num_groups=num_groups,
+            group_topk=group_topk, scaling_factor=scaling_factor)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(logits, ids, probs, counts)
+        ctx.router = (score_function, scaling_factor)
         ctx.mark_non_differentiable(ids, counts, offsets, dest, token_of_row, row_prob)
         return probs, ids, counts, offsets, dest, token_of_row, row_prob, aux   # aux: None without aux_loss
 
@@ -253,10 +283,30 @@ class _Route(torch.autograd.Function):
             dprobs = dprobs.float().contiguous()
         if d_aux is not None:
             d_aux = d_aux.float().reshape(1).contiguous()
-        return _ext.require().moe_route_bwd(logits, ids, probs, dprobs, counts, d_aux), None, None
+        dlogits = _ext.require().moe_route_bwd(logits, ids, probs, dprobs, counts, d_aux, score_function=ctx.router[0],
+                                               scaling_factor=ctx.router[1])
+        return (dlogits,) + (None,) * 7
 
 
-def moe_route(logits, topk, aux_loss=False, fused=None):
+def _check_sigmoid_options(E, topk, expert_bias, num_groups, group_topk, logits):
+    if (num_groups is None) != (group_topk is None):
+        raise ValueError("moe_route: num_groups and group_topk go together")
+    if num_groups is not None:
+        if not (1 <= num_groups <= 16 and E % num_groups == 0 and E // num_groups >= 2):
+            raise ValueError(f"moe_route: num_groups={num_groups} must be in [1, 16], divide E={E} and leave two "
+                             "experts per group")
+        if not 1 <= group_topk <= num_groups:
+            raise ValueError(f"moe_route: group_topk={group_topk} must be in [1, num_groups={num_groups}]")
+        if topk > group_topk * (E // num_groups):
+            raise ValueError(f"moe_route: topk={topk} exceeds the {group_topk * (E // num_groups)} experts of "
+                             f"{group_topk} groups")
+    if expert_bias is not None and (expert_bias.shape != (E,) or expert_bias.dtype != torch.float32
+                                    or expert_bias.device != logits.device):
+        raise ValueError("moe_route: expert_bias must be an fp32 [E] tensor on logits' device")
+
+
+def moe_route(logits, topk, aux_loss=False, fused=None, *, score_function="softmax", expert_bias=None,
+              num_groups=None, group_topk=None, scaling_factor=1.0):
     """Route tokens to their ``topk`` experts. ``logits [T, E]`` (fp32, fp16 or bf16; used in fp32). Returns a
     :class:`Routing`: ``expert_ids`` are the ``topk`` largest logits of every token in descending order, equal
     logits going to the lowest expert index; ``probs`` the softmax over those ``topk`` logits; ``offsets``,
@@ -269,13 +319,50 @@ def moe_route(logits, topk, aux_loss=False, fused=None):
     Device logits within ``moe_route_supported`` run csrc/moe_route.hip: three launches forward, one backward,
     no atomics, nothing read on the host, bit-reproducible. CPU tensors, ``APEX_FORCE_REFERENCE=1`` and other
     shapes take a stable sort in PyTorch with the same outputs. ``fused``: None takes the kernels where they
-    were measured faster (``E < 64`` or ``topk <= 2``), True insists on them, False on the PyTorch path."""
+    were measured faster (``E < 64`` or ``topk <= 2``), True insists on them, False on the PyTorch path.
+
+    ``score_function="sigmoid"`` is the router of the wide top-8 models (DeepSeek-V3; Megatron-Core's
+    ``moe_router_score_function`` and its companions), and the only one that takes the other four options:
+
+    1. the score is ``s = sigmoid(logits)``;
+    2. the key ``s + expert_bias`` (a finite fp32 ``[E]`` constant; without one the key is ``s``) decides the
+       selection and nothing else;
+    3. with ``num_groups = G`` expert ``e`` is in group ``e // (E / G)`` (``E % G == 0``, ``E / G >= 2``, ``G <=
+       16``), a group's score is the sum of its two largest keys, and only the experts of the ``group_topk``
+       groups with the largest scores (ties to the lowest group) can be chosen; ``topk <= group_topk * E / G``;
+    4. ``expert_ids`` are the ``topk`` eligible experts with the largest keys, descending, ties to the lowest index;
+    5. ``probs = scaling_factor * s / (sum of the chosen s + 1e-20)``, and ``scaling_factor * s`` for ``topk == 1``;
+    6. ``aux_loss`` takes ``s / (sum_e s + 1e-20)`` in place of the softmax;
+    7. the row maps and the gradients are as above; experts a token did not choose get an exactly zero gradient
+       from ``probs``.
+
+    Its kernels (same file, same three-plus-one launches) split the work for wide ``E``, and ``fused=None`` takes
+    them wherever they are supported: they were measured faster at every shape timed."""
     if logits.dim() != 2 or not 1 <= topk <= logits.shape[1]:
         raise ValueError(f"moe_route: logits [T, E] and 1 <= topk <= E, got {tuple(logits.shape)} and topk={topk}")
+    if score_function not in ("softmax", "sigmoid"):
+        raise ValueError(f"moe_route: score_function must be 'softmax' or 'sigmoid', got {score_function!r}")
+    sigmoid = score_function == "sigmoid"
+    if not sigmoid and (expert_bias is not None or num_groups is not None or group_topk is not None
+                        or scaling_factor != 1.0):
+        raise ValueError("moe_route: expert_bias, num_groups, group_topk and scaling_factor need "
+                         "score_function='sigmoid'")
     native = _ext.use_native(logits) and logits.dtype in (torch.float32,) + _HALF and logits.numel() > 0 \
         and moe_route_supported(logits.shape[0], logits.shape[1], topk, logits.dtype)
     if fused and not native:
         raise ValueError("moe_route: fused=True needs device logits within moe_route_supported")
+    if sigmoid:
+        _check_sigmoid_options(logits.shape[1], topk, expert_bias, num_groups, group_topk, logits)
+        opts = (None if expert_bias is None else expert_bias.detach().contiguous(), int(num_groups or 0),
+                int(group_topk or 0), float(scaling_factor))
+        if fused is None:
+            # profiles/moe_route_sigmoid_vs_torch.jsonl: the kernels are faster than the PyTorch formulation at
+            # every shape timed (T = 4096 / 16384, E = 8 / 64 / 128 / 256, topk = 2 / 4 / 8, with and without
+            # groups, forward and forward + backward; by 1.5x at the least), so wherever they are supported
+            fused = native
+        if fused:
+            return Routing(*_Route.apply(logits.contiguous(), int(topk), bool(aux_loss), "sigmoid", *opts))
+        return _sigmoid_reference(logits, int(topk), bool(aux_loss), *opts)
     if fused is None:
         # profiles/moe_route_vs_torch.jsonl: with one token per wave pass (E >= 64) the kernels lose to the
         # PyTorch formulation at topk = 8 and win at topk = 2; nothing between was measured

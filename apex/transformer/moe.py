@@ -3,7 +3,7 @@ run as grouped GEMMs on expert-sorted tokens (apex.ops.grouped), with no host re
 Switch / Megatron load-balancing auxiliary loss.
 
 Out of scope here: expert parallelism, tensor-parallel (sharded) experts, capacity limits and token dropping,
-sigmoid or group-limited routing, a router z-loss, and fp8 / MX experts.
+a router z-loss, sequence-level auxiliary losses, and fp8 / MX experts.
 """
 from __future__ import annotations
 
@@ -61,10 +61,18 @@ class MoEMLP(nn.Module):
     Parameters: ``router.weight [E, hidden]``, ``w1 [E, ffn_hidden (x 2 when gated), hidden]``, ``w2 [E, hidden,
     ffn_hidden]``. After a forward, ``router_probs`` is the gate ``[tokens, topk]`` (fp32, attached to the graph),
     ``expert_ids`` the chosen experts and ``tokens_per_expert`` their counts ``[E]`` (both int64). See the
-    module docstring for what is out of scope."""
+    module docstring for what is out of scope.
+
+    ``score_function="sigmoid"`` with ``num_groups`` / ``group_topk`` and ``scaling_factor`` selects the sigmoid,
+    group-limited router of ``apex.ops.moe_route`` (the gate is then the normalised, scaled sigmoid score).
+    ``expert_bias=True`` adds the aux-loss-free balancing of that router: the fp32 buffer ``expert_bias [E]``
+    enters the selection only, every training forward adds its token counts to the buffer
+    ``tokens_per_expert_acc [E]`` (no host read), and :meth:`update_expert_bias`, called once per optimizer step,
+    moves the bias towards the under-loaded experts."""
 
     def __init__(self, hidden, ffn_hidden, num_experts, topk=2, activation="gelu", init_std=0.02, out_std=None,
-                 params_dtype=torch.float32, aux_loss_coeff=0.0):
+                 params_dtype=torch.float32, aux_loss_coeff=0.0, score_function="softmax", num_groups=None,
+                 group_topk=None, scaling_factor=1.0, expert_bias=False):
         super().__init__()
         if activation not in _ACTS:
             raise ValueError(f"activation must be 'gelu', 'swiglu' or 'geglu', got {activation!r}")
@@ -72,6 +80,19 @@ class MoEMLP(nn.Module):
             raise ValueError(f"topk={topk} must be in [1, num_experts={num_experts}]")
         self.num_experts, self.topk, self.gated_act = num_experts, topk, _ACTS[activation]
         self.aux_loss_coeff = float(aux_loss_coeff)
+        if score_function not in ("softmax", "sigmoid"):
+            raise ValueError(f"score_function must be 'softmax' or 'sigmoid', got {score_function!r}")
+        if score_function != "sigmoid" and (num_groups is not None or group_topk is not None or expert_bias
+                                            or scaling_factor != 1.0):
+            raise ValueError("num_groups, group_topk, scaling_factor and expert_bias need score_function='sigmoid'")
+        self.route_options = dict(score_function=score_function)
+        if score_function == "sigmoid":
+            self.route_options.update(num_groups=num_groups, group_topk=group_topk, scaling_factor=scaling_factor)
+        if expert_bias:
+            self.register_buffer("expert_bias", torch.zeros(num_experts, dtype=torch.float32))
+            self.register_buffer("tokens_per_expert_acc", torch.zeros(num_experts, dtype=torch.float32))
+        else:
+            self.expert_bias = None
         self.router = nn.Linear(hidden, num_experts, bias=False, dtype=params_dtype)
         f1 = ffn_hidden if self.gated_act is None else 2 * ffn_hidden
         self.w1 = nn.Parameter(torch.empty(num_experts, f1, hidden, dtype=params_dtype))
@@ -90,9 +111,13 @@ class MoEMLP(nn.Module):
 
     def forward(self, x):
         x2 = x.reshape(-1, x.shape[-1])
-        r = moe_route(self.router(x2), self.topk, aux_loss=self.aux_loss_coeff != 0.0)
+        bias = {} if self.expert_bias is None else dict(expert_bias=self.expert_bias.float())
+        r = moe_route(self.router(x2), self.topk, aux_loss=self.aux_loss_coeff != 0.0, **self.route_options, **bias)
         self.router_probs, self.expert_ids = r.probs, r.expert_ids.long()
         self.tokens_per_expert = r.tokens_per_expert.long()
+        if self.expert_bias is not None and self.training:
+            with torch.no_grad():
+                self.tokens_per_expert_acc += r.tokens_per_expert
         xp, offsets, dest = moe_permute(x2, r.expert_ids, self.num_experts, routing=r)
         h = self._act(grouped_linear(xp, self.w1, offsets))   # zero rows stay zero through all three activations
         out = moe_unpermute(grouped_linear(h, self.w2, offsets), dest, r.probs, routing=r)
@@ -102,6 +127,16 @@ class MoEMLP(nn.Module):
             self.aux_loss = aux.detach()
             out = _AuxLossScaler.apply(out, aux)
         return out.view(x.shape), None
+
+    @torch.no_grad()
+    def update_expert_bias(self, rate):
+        """``expert_bias += rate * sign(mean(acc) - acc)`` over the token counts accumulated since the last call,
+        then the accumulator is zeroed: experts that got fewer tokens than the average become more likely."""
+        if self.expert_bias is None:
+            raise RuntimeError("update_expert_bias needs MoEMLP(..., expert_bias=True)")
+        acc = self.tokens_per_expert_acc
+        self.expert_bias += rate * torch.sign(acc.mean() - acc)
+        acc.zero_()
 
     def extra_repr(self):
         return f"experts={self.num_experts}, topk={self.topk}, w1={tuple(self.w1.shape)}, w2={tuple(self.w2.shape)}"

@@ -2133,12 +2133,34 @@ std::vector<Tensor> route_alloc(apex::MoeRouteArgs& a, int64_t T, int64_t E, int
 }
 
 // logits [T, E] -> (probs, expert_ids, tokens_per_expert, offsets, dest, token_of_row, row_prob, aux or None)
-std::vector<c10::optional<Tensor>> k_moe_route_fwd(Tensor logits, int64_t topk, bool aux) {
+// score_function "sigmoid" takes the sigmoid router's kernel; expert_bias, the groups and the scaling factor are its
+bool route_sigmoid(const std::string& score_function, const Tensor& logits, const c10::optional<Tensor>& expert_bias,
+                   int64_t num_groups, int64_t group_topk, double scaling_factor, const char* who) {
+  const bool sig = score_function == "sigmoid";
+  TORCH_CHECK(sig || score_function == "softmax", who, ": score_function must be 'softmax' or 'sigmoid'");
+  TORCH_CHECK(sig || (!has(expert_bias) && num_groups == 0 && group_topk == 0 && scaling_factor == 1.0), who,
+              ": expert_bias, num_groups, group_topk and scaling_factor need score_function='sigmoid'");
+  TORCH_CHECK(!has(expert_bias) || (expert_bias->device() == logits.device() && expert_bias->scalar_type() == at::kFloat &&
+                                    expert_bias->is_contiguous() && expert_bias->dim() == 1 &&
+                                    expert_bias->size(0) == logits.size(1)),
+              who, ": expert_bias must be a contiguous fp32 [E] tensor on logits' device");
+  return sig;
+}
+
+std::vector<c10::optional<Tensor>> k_moe_route_fwd(Tensor logits, int64_t topk, bool aux,
+                                                   const std::string& score_function,
+                                                   const c10::optional<Tensor>& expert_bias, int64_t num_groups,
+                                                   int64_t group_topk, double scaling_factor) {
   TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.is_contiguous() &&
                   k_moe_route_supported(logits.size(0), logits.size(1), topk, logits.scalar_type()),
               "moe_route_fwd: unsupported operands");
   const int64_t T = logits.size(0), E = logits.size(1);
+  const bool sig = route_sigmoid(score_function, logits, expert_bias, num_groups, group_topk, scaling_factor,
+                                 "moe_route_fwd");
+  TORCH_CHECK(apex::moe_route_groups_ok(E, topk, num_groups, group_topk), "moe_route_fwd: unsupported groups");
   apex::MoeRouteArgs a{};
+  a.expert_bias = opt_ptr<float>(expert_bias);
+  a.num_groups = (int)num_groups, a.group_topk = (int)group_topk, a.scaling = (float)scaling_factor;
   std::vector<Tensor> work;
   auto out = route_alloc(a, T, E, topk, aux, logits.options(), work);
   const auto fo = logits.options().dtype(at::kFloat);
@@ -2150,7 +2172,10 @@ std::vector<c10::optional<Tensor>> k_moe_route_fwd(Tensor logits, int64_t topk, 
   a.row_prob = row_prob.data_ptr<float>();
   a.aux = aux ? aux_t->data_ptr<float>() : nullptr;
   hipStream_t s = cur_stream();
-  check(apex::moe_route_topk(a, dt_code(logits.scalar_type()), s), "moe_route_topk");
+  if (sig)
+    check(apex::moe_route_sigmoid_topk(a, dt_code(logits.scalar_type()), s), "moe_route_sigmoid_topk");
+  else
+    check(apex::moe_route_topk(a, dt_code(logits.scalar_type()), s), "moe_route_topk");
   check(apex::moe_route_scan(a, s), "moe_route_scan");
   check(apex::moe_route_place(a, s), "moe_route_place");
   return {probs, out[0], out[1], out[2], out[3], out[4], row_prob, aux_t};
@@ -2175,7 +2200,8 @@ std::vector<Tensor> k_moe_route_maps(Tensor expert_ids, int64_t E) {
 }
 
 Tensor k_moe_route_bwd(Tensor logits, Tensor expert_ids, Tensor probs, const c10::optional<Tensor>& dprobs,
-                       Tensor tokens_per_expert, const c10::optional<Tensor>& d_aux) {
+                       Tensor tokens_per_expert, const c10::optional<Tensor>& d_aux, const std::string& score_function,
+                       double scaling_factor) {
   TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.is_contiguous() && expert_ids.dim() == 2 &&
                   expert_ids.size(0) == logits.size(0) && grouped_index_ok(expert_ids, expert_ids) &&
                   expert_ids.device() == logits.device() &&
@@ -2196,6 +2222,13 @@ Tensor k_moe_route_bwd(Tensor logits, Tensor expert_ids, Tensor probs, const c10
   a.probs = probs.data_ptr<float>();
   a.tokens_per_expert = tokens_per_expert.data_ptr<int>();
   Tensor dlogits = at::empty_like(logits);
+  if (route_sigmoid(score_function, logits, c10::nullopt, 0, 0, scaling_factor, "moe_route_bwd")) {
+    a.scaling = (float)scaling_factor;
+    check(apex::moe_route_sigmoid_bwd(a, opt_ptr<float>(dprobs), opt_ptr<float>(d_aux), dlogits.data_ptr(),
+                                      dt_code(logits.scalar_type()), cur_stream()),
+          "moe_route_sigmoid_bwd");
+    return dlogits;
+  }
   check(apex::moe_route_bwd(a, opt_ptr<float>(dprobs), opt_ptr<float>(d_aux), dlogits.data_ptr(),
                             dt_code(logits.scalar_type()), cur_stream()),
         "moe_route_bwd");
@@ -2348,9 +2381,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_combine", &k_moe_combine, py::arg("src"), py::arg("dest"), py::arg("w") = py::none(),
         py::arg("g") = py::none(), py::arg("want_out") = true);
   m.def("moe_route_supported", &k_moe_route_supported);
-  m.def("moe_route_fwd", &k_moe_route_fwd, py::arg("logits"), py::arg("topk"), py::arg("aux") = false);
+  m.def("moe_route_fwd", &k_moe_route_fwd, py::arg("logits"), py::arg("topk"), py::arg("aux") = false,
+        py::arg("score_function") = "softmax", py::arg("expert_bias") = py::none(), py::arg("num_groups") = 0,
+        py::arg("group_topk") = 0, py::arg("scaling_factor") = 1.0);
   m.def("moe_route_maps", &k_moe_route_maps);
-  m.def("moe_route_bwd", &k_moe_route_bwd);
+  m.def("moe_route_bwd", &k_moe_route_bwd, py::arg("logits"), py::arg("expert_ids"), py::arg("probs"),
+        py::arg("dprobs"), py::arg("tokens_per_expert"), py::arg("d_aux"), py::arg("score_function") = "softmax",
+        py::arg("scaling_factor") = 1.0);
   m.def("gemm_tt_f8_supported", &k_gemm_tt_f8_supported);
   m.def("gemm_tt_f8", &k_gemm_tt_f8, py::arg("a"), py::arg("b"), py::arg("alpha_a"), py::arg("alpha_b"),
         py::arg("fmt_a"), py::arg("fmt_b"), py::arg("splits"), py::arg("out_dtype"), py::arg("out") = py::none());

@@ -424,6 +424,10 @@ struct MoeRouteArgs {
   int* dest;               // [T, topk]
   int* token_of_row;       // [R], -1 on pad and tail rows
   float* row_prob;         // [R], 0 on pad and tail rows
+  // the sigmoid router only (zero-initialised elsewhere)
+  const float* expert_bias;    // [E] fp32 added to the scores for selection only, or null
+  int num_groups, group_topk;  // group-limited selection; 0, 0: none
+  float scaling;               // the gate's scaling factor
 };
 // 1 <= topk <= kMoeMaxTopk, topk <= E <= 256, T >= 1, T * topk + 64 * E < 2^31
 bool moe_route_supported(int64_t T, int64_t E, int64_t topk, int dt);
@@ -434,6 +438,15 @@ int moe_route_place(const MoeRouteArgs& a, hipStream_t s);
 // dlogits [T, E] in the logits' dtype from dprobs [T, topk] and the device scalar d_aux (either may be null)
 int moe_route_bwd(const MoeRouteArgs& a, const float* dprobs, const float* d_aux, void* dlogits, int dt,
                   hipStream_t s);
+// The sigmoid router: key = sigmoid(logit) + expert_bias selects (group-limited with num_groups > 0: the
+// group_topk groups with the largest sum of their two largest keys), gate = scaling * s / (sum of the chosen s +
+// 1e-20), un-normalised for topk == 1; the aux loss takes s / (sum_e s + 1e-20) for the softmax. Replaces
+// moe_route_topk / moe_route_bwd; scan and place are shared.
+// num_groups == group_topk == 0, or E % G == 0, E / G >= 2, G <= 16, 1 <= group_topk <= G, topk <= group_topk * E / G
+bool moe_route_groups_ok(int64_t E, int64_t topk, int64_t num_groups, int64_t group_topk);
+int moe_route_sigmoid_topk(const MoeRouteArgs& a, int dt, hipStream_t s);
+int moe_route_sigmoid_bwd(const MoeRouteArgs& a, const float* dprobs, const float* d_aux, void* dlogits, int dt,
+                          hipStream_t s);
 
 // ----------------------------- input pipeline (K-09) -----------------------
 // layout: 0 NHWC->NHWC, 1 NHWC->NCHW (hw % 8 == 0, C in {1,3,4}), 2 NCHW->NCHW. Returns 1 if

@@ -10,6 +10,10 @@ a stable sort, softmax, _routing_maps), not a copy of it. Per shape the two vari
 are sampled in turn, round after round, in one process, so a clock drift or a neighbour on the host lands on
 both alike; a sample is `iters` calls between two device events; the graphics clock is sampled while the rounds
 run. Reported: median / min / max microseconds per call. The first row of a run records the command line.
+
+--router sigmoid times the sigmoid router instead (profiles/moe_route_sigmoid_vs_torch.jsonl): score_function=
+"sigmoid" with an expert bias and scaling_factor 2.5, E in {8, 64, 128, 256}, topk in {2, 4, 8}, without groups and
+(E >= 64) with num_groups = 8, group_topk = 4; the PyTorch formulation is again fused=False of the same call.
 """
 import argparse
 import json
@@ -27,6 +31,7 @@ def main():
     ap.add_argument("out")
     ap.add_argument("--samples", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--router", choices=("softmax", "sigmoid"), default="softmax")
     args = ap.parse_args()
 
     from apex import _ext
@@ -66,24 +71,29 @@ def main():
                               iters=args.iters, sclk_mhz=clock))
             print(json.dumps(lines[-1]), flush=True)
 
+    sig = args.router == "sigmoid"
     for T in (4096, 16384):
-        for E in (8, 64, 256):
-            for topk in (2, 8):
+        for E in (8, 64, 128, 256) if sig else (8, 64, 256):
+            for topk, G in [(k, G) for k in ((2, 4, 8) if sig else (2, 8)) for G in ((None, 8) if sig and E >= 64 else (None,))]:
                 torch.manual_seed(0)
                 logits = torch.randn(T, E, device="cuda").bfloat16().requires_grad_()
                 g = torch.randn(T, topk, device="cuda")
+                kw = {}
+                if sig:
+                    kw = dict(score_function="sigmoid", scaling_factor=2.5, num_groups=G, group_topk=G and 4,
+                              expert_bias=torch.randint(-4, 5, (E,), device="cuda").float() / 8)
 
                 def fwd(fused=True):
-                    return moe_route(logits, topk, aux_loss=True, fused=fused)
+                    return moe_route(logits, topk, aux_loss=True, fused=fused, **kw)
 
                 def fwd_bwd(fused=True):
-                    r = moe_route(logits, topk, aux_loss=True, fused=fused)
+                    r = moe_route(logits, topk, aux_loss=True, fused=fused, **kw)
                     return torch.autograd.grad((r.probs * g).sum() + r.aux_loss, logits)
 
                 a, b = fwd(), reference(fwd)()
                 same = all(torch.equal(getattr(a, n), getattr(b, n)) for n in
                            ("expert_ids", "tokens_per_expert", "offsets", "dest", "token_of_row"))
-                extra = dict(T=T, E=E, topk=topk, maps_equal=same,
+                extra = dict(T=T, E=E, topk=topk, **(dict(router="sigmoid", num_groups=G) if sig else {}), maps_equal=same,
                              probs_max_diff=float((a.probs - b.probs).abs().max()))
                 run({"fused_fwd": fwd, "torch_fwd": reference(fwd)}, extra)
                 run({"fused_fwd_bwd": fwd_bwd, "torch_fwd_bwd": reference(fwd_bwd)}, extra)
